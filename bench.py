@@ -20,12 +20,18 @@ still in flight.  `--lanes 1` = every step waits for its own read-back (`single_
 Multi-GPU: every rank is a replica with its
 own batch (weak scaling, no data-path collective; RCCL only for the barrier / max-time).
 
-Prints ONE JSON line on rank 0 (see the task contract): value = whole-job frames/s.
-`roofline` is measured live with HIP events around the dominant kernel (the largest single
+Prints ONE JSON line on rank 0 (see the task contract): value = whole-job frames/s, ms_per_step = one
+timed step.  A plain run does only that: set-up, the untimed wake-up windows and the W warm-up steps, the
+K timed steps, the outputs (--dump-outputs DIR) and the line.  Everything else is measured with --full:
+`roofline` live with HIP events around the dominant kernel (the largest single
 entry of the rocprofv3 kernel stats: block1_mx_kernel) inside the timed region; the match, the two 24->24 convolutions and the
 whole MFMA convolution family are reported next to it from short untimed passes of the same step;
-`cpu_baseline` times the CPU oracle (a port of the reference's CPU path) on the host cores
+the side figures and workloads, the GPU state around the timed region, and
+`cpu_baseline`, which times the CPU oracle (a port of the reference's CPU path) on the host cores
 for a bounded sample.
+
+--dump-outputs DIR writes what the last timed step returned (FrameStream.result() of the last batch) as
+DIR/<name>.npy: see dump_outputs().  The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import ctypes as C
@@ -170,6 +176,16 @@ class GpuStateSampler:
         return out
 
 
+def host_threads():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS when that is set (os.cpu_count() counts the whole machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS") or n))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baseline(seconds):
     """Oracle (port of the reference CPU path) on the host cores: same workload shape,
     bounded sample: batches of 4 VGA frames + their 2 pair matches, repeated ~`seconds`."""
@@ -177,7 +193,7 @@ def cpu_baseline(seconds):
     from oracle import xfeat_oracle as O
     sd = fixtures.synthetic_state_dict(0)
     x = make_frames(4, seed=77)
-    ncpu = os.cpu_count() or 1
+    ncpu = host_threads()
     # torch's CPU conv path does not scale to hundreds of threads on these small maps (it gets
     # slower): pick the fastest thread count from a short calibration and report it.
     best = None
@@ -222,8 +238,7 @@ def cpu_baseline(seconds):
 
 def cpu_sample(seconds, fn, unit, units_per_call, what):
     """Bounded CPU-oracle sample for the secondary workloads: repeat fn() for about `seconds`."""
-    ncpu = os.cpu_count() or 1
-    threads = min(ncpu, 32)
+    threads = min(host_threads(), 32)
     torch.set_num_threads(threads)
     n, used = 0, 0.0
     while used < seconds or n < 1:
@@ -715,19 +730,47 @@ def close_group(dist):
         os._exit(0)
 
 
+def dump_outputs(path, r, desc_rows=1024, seed=0):
+    """--dump-outputs: the arrays FrameStream.result() returned for the last timed batch, as path/<name>.npy in float32 (coordinates, scores,
+    descriptors) or float64 (indices and counts, exact).  Rows past an image's n_valid or a pair's n_matches are unspecified on the device and
+    are written as 0 (key-points, scores, descriptors) or -1 (match indices), so that two builds compare element for element.  The descriptors
+    (B x top_k x 64 fp32: 64 MiB) are a fixed seeded sample of `desc_rows` key-point rows, the same rows of every image
+    (descriptor_sample_rows.npy); about 21 MiB in all at the bench shape."""
+    os.makedirs(path, exist_ok=True)
+    nv, nm = r["n_valid"].numpy().astype(np.int64), r["n_matches"].numpy().astype(np.int64)
+    K = r["keypoints"].shape[1]
+    rows = np.sort(np.random.RandomState(seed).choice(K, min(desc_rows, K), replace=False))
+    kp = r["keypoints"].float().cpu().numpy()
+    sc = r["scores"].float().cpu().numpy()
+    de = r["descriptors"][:, torch.from_numpy(rows).to(r["descriptors"].device)].float().cpu().numpy()
+    i0, i1 = r["idx0"].cpu().numpy().astype(np.float64), r["idx1"].cpu().numpy().astype(np.float64)
+    kv = np.arange(K)[None, :] < nv[:, None]
+    mv = np.arange(i0.shape[1])[None, :] < nm[:, None]
+    kp[~kv], sc[~kv], de[~kv[:, rows]] = 0.0, 0.0, 0.0
+    i0[~mv], i1[~mv] = -1.0, -1.0
+    arrays = {"keypoints": kp, "scores": sc, "descriptors_sample": de, "descriptor_sample_rows": rows.astype(np.float64), "idx0": i0, "idx1": i1,
+              "n_valid": nv.astype(np.float64), "n_candidates": r["n_candidates"].numpy().astype(np.float64), "n_matches": nm.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step (BASELINE config: 64)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bound of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure: roofline and per-kernel passes, side figures and workloads, "
+                                                        "GPU state, CPU baseline (off: set-up, warm-up, the timed steps, --dump-outputs and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bound of the CPU-baseline sample of --full (0 = skip)")
     ap.add_argument("--lanes", type=int, default=2, help="batches in flight per GPU (accelerated_features_amd.streaming.FrameStream: one handle + HIP stream each); "
                                                          "1 = every step waits for its own read-back")
     ap.add_argument("--concurrent-lanes", type=int, default=1, help="1 (default): a HIP stream per lane (FrameStream(concurrent=True)): one batch's convolutions fill the other's "
                                                                         "latency-bound tail; 0: all lanes on one stream (the kernels run one after the other as in the synchronous path)")
     ap.add_argument("--wake-ms", type=float, default=200.0, help="untimed steps for this many ms before the profiling passes and the warm-up (a cold GPU's first ~150 ms run 3-4 %% slow); 0 = none")
-    ap.add_argument("--no-side-passes", action="store_true", help="skip the extraction-only / with-H2D side figures (profiling runs)")
+    ap.add_argument("--no-side-passes", action="store_true", help="skip the extraction-only / with-H2D side figures of --full (profiling runs)")
     ap.add_argument("--workload", default="sparse", choices=["sparse", "dense", "lighterglue", "megadepth", "demo"],
                     help="sparse = BASELINE configs[1] (the contract metric); dense = configs[2], match_xfeat_star on 1024^2 pairs, batch 32; "
                          "megadepth = configs[3], the MegaDepth-1500 pair list sharded across the GPUs; lighterglue = configs[4]; "
@@ -741,6 +784,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.workload != "sparse":
+        raise SystemExit("--dump-outputs is implemented for the sparse workload (the headline) only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started without a launcher: become the launcher.  One process per GPU under torch.distributed.run; fewer visible GPUs than asked
         # for is an error, never a line with a smaller n_gpus.
@@ -802,29 +847,42 @@ def main():
     handles = [l.net.handle() for l in lane_xf]
     fs = FrameStream(xfeats=lane_xf, top_k=TOP_K, detection_threshold=0.05, min_cossim=-1, concurrent=conc)
     retired = []
+    window = min(args.steps, 20)                           # steps per untimed wake-up window (and per --full repeat window): their cost does not grow with --steps
 
     timed_calls = [None]                                   # calls left in the timed region (None: warm-up)
+    timed_retired = [0]                                    # batches retired inside the timed region
+
+    def retire(rs):
+        if timed_calls[0] is not None and rs:              # timed region: only the newest result is kept (K retained batches, ~70 MB of device tensors each, would fill HBM at large K)
+            timed_retired[0] += len(rs)
+            retired[:] = rs[-1:]
+        else:
+            retired.extend(rs)
 
     def lane_step():
         r = None
         if fs.in_flight == fs.lanes:
             r = fs.result()
-            retired.append(r)
+            retire([r])
         fs.submit(x)
         if timed_calls[0] is not None:
             timed_calls[0] -= 1
             if timed_calls[0] == 0:                        # the last timed step also retires what is still in flight: all K results are delivered inside the region
-                retired.extend(fs.drain())
+                retire(fs.drain())
         return r
+
+    def capacity_ok(rs):
+        return all(int(r["n_candidates"].max()) <= r["nms_capacity"] for r in rs)
 
     def arm(last):
         for r in fs.drain():                               # nothing of the warm-up is in flight when the timed region starts
             retired.append(r)
-        assert retired and all(int(r["n_candidates"].max()) <= r["nms_capacity"] for r in retired), "NMS capacity overflow in the benchmark workload"
+        assert capacity_ok(retired), "NMS capacity overflow in the benchmark workload"
         retired.clear()
         timed_calls[0] = args.steps
-        for h_ in handles:
-            lib.xfh_profile_select(h_, _lib.PROF_BLOCK1)
+        if args.full:
+            for h_ in handles:
+                lib.xfh_profile_select(h_, _lib.PROF_BLOCK1)
 
     def read_prof(hs=None):
         tot = [0, 0.0, 0.0, 0.0]
@@ -860,25 +918,26 @@ def main():
     # GPU wake-up BEFORE the warm-up.  A GPU that has just been woken delivers 3-4 % less for its first ~150 ms of work (power state: bench.py --warmup 5 alone
     # 38.8 k frames/s, --warmup 40 40.2 k, every later window of the same run 40-41.8 k; a kernel span measured cold read 386 us for block1 against 245):
     # untimed windows of steps (at least --wake-ms, until two windows in a row agree within 1 %) bring it to the state a stream of batches runs in; block1's HIP events are created here (hipEventCreate inside
-    # the timed region cost its first window 1.8 %).  Then the contract's W warm-up steps and K timed steps, back to back.
-    for h_ in handles:
-        lib.xfh_profile_select(h_, _lib.PROF_BLOCK1)
+    # the timed region cost its first window 1.8 %).  Then the contract's W warm-up steps and K timed steps, back to back.  (A plain run selects no events at all.)
+    if args.full:
+        for h_ in handles:
+            lib.xfh_profile_select(h_, _lib.PROF_BLOCK1)
     # sclk / power are sampled WHILE THE WAKE-UP WINDOWS RUN (the same steps as the timed region, untimed), not inside the timed region: a thread that reads the SMU's sysfs nodes
     # once per millisecond beside the thread that launches 88 kernels per millisecond cost the timed steps 2-4 % (value against the windows measured right after it, which had no
     # sampler: 53.3 / 54.6 k, 52.7 / 54.6, 53.6 / 55.7 and once 48.6 / 55.8; round 5, without a sampler: 49.8 / 49.7-50.5)
-    tele_before = gpu_telemetry(local_rank)
-    sampler = GpuStateSampler(local_rank, period_s=0.005).start() if args.wake_ms > 0 else None
+    tele_before = gpu_telemetry(local_rank) if args.full else None
+    sampler = GpuStateSampler(local_rank, period_s=0.005).start() if args.wake_ms > 0 and args.full else None
     t_wake, n_wake, wake_rates = time.perf_counter(), 0, []
-    while args.wake_ms > 0:                                # windows of `steps` untimed steps until two in a row agree within 1 % (and >= wake_ms, <= 8 x wake_ms have passed)
+    while args.wake_ms > 0:                                # windows of `window` untimed steps until two in a row agree within 1 % (and >= wake_ms, <= 8 x wake_ms have passed)
         torch.cuda.synchronize()
         t0w = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(window):
             lane_step()
         fs.drain()
         retired.clear()                                    # (window by window: 160 retained results are 11 GB whose release right in front of the warm-up is an idle gap)
         torch.cuda.synchronize()
-        wake_rates.append(B * args.steps / (time.perf_counter() - t0w))
-        n_wake += args.steps
+        wake_rates.append(B * window / (time.perf_counter() - t0w))
+        n_wake += window
         el = (time.perf_counter() - t_wake) * 1e3
         settled = len(wake_rates) >= 2 and abs(wake_rates[-1] / wake_rates[-2] - 1.0) < 0.01
         if (el >= args.wake_ms and settled) or el >= 8 * args.wake_ms:
@@ -893,13 +952,54 @@ def main():
     # (nothing between the wake-up windows and the warm-up: the single reads of the sysfs nodes -- a dozen SMU queries with the GPU idle -- used to sit here and cost the timed
     #  region the state the wake-up had just established: value 3.5 % below the windows measured before and after it.  `before` is now read in front of the wake-up.)
     dt_max, _ = sharding.timed_steps(lane_step, args.steps, args.warmup, dist, torch.cuda.synchronize, "cuda", before_timed=arm)
-    tele_after = gpu_telemetry(local_rank)
+    tele_after = gpu_telemetry(local_rank) if args.full else None
     tele_during = sampler.stop() if sampler else {"samples": 0}
     timed_calls[0] = None
-    assert len(retired) == args.steps and fs.in_flight == 0
+    assert timed_retired[0] == args.steps and fs.in_flight == 0
     last = retired[-1]
+    assert capacity_ok([last]), "NMS capacity overflow in the benchmark workload"
     counts = torch.cat([last["n_valid"], last["n_candidates"], last["n_matches"]])
     cap = last["nms_capacity"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    retired.clear()
+
+    n_valid = counts[:B].tolist()
+    n_match = counts[2 * B:].tolist()
+    fps = sharding.aggregate_rate(B, args.steps, world, dt_max, "weak")
+    headline = {
+        "metric": "frames/sec detectAndCompute+match (VGA, top_k=4096)",
+        "value": round(fps, 2),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt_max / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "VGA 640x480 sparse top_k=4096, batch=64 per GPU: detectAndCompute + MNN match of "
+                               "the 32 consecutive frame pairs (BASELINE configs[1])",
+                   "batch_per_gpu": B, "height": H, "width": W, "top_k": TOP_K, "weights": "synthetic (tests/fixtures.py)",
+                   "arithmetic": "fp32 results; the 24-, 64- and 128-channel 3x3 convolutions, block1.2/.3 and both heads on fp16 MFMAs with an fp16 PAIR per operand "
+                                 "(x = xh + 2^-11 xl: three MFMAs per product, error <= an fp32 direct convolution's; range-guarded, the f32-MFMA / vector-ALU kernels as fallback); "
+                                 "the matcher decides on exact fp32 dot products (fp16 MFMAs only pre-select 32-wide blocks inside a derived error window)",
+                   "parallelism": f"replicas x{world}, no collective; {lanes} batches in flight per GPU (FrameStream), "
+                                  + ("a HIP stream per lane" if conc else "all lanes on one HIP stream"),
+                   "barrier": args.barrier_name,
+                   "concurrent_lanes": conc,
+                   "lanes": lanes,
+                   "untimed_before_the_timed_region": f"GPU wake-up ({n_wake} steps: windows of {window} until two agree within 1 %, >= {args.wake_ms:.0f} ms; a cold GPU runs its first ~150 ms 3-4 % slow), then the W warm-up steps",
+                   "wake_up_window_fps": [round(r, 1) for r in wake_rates],
+                   "mean_keypoints": round(float(np.mean(n_valid)), 1), "mean_matches": round(float(np.mean(n_match)), 1)},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
+        close_group(dist)
+        return
 
     n_l, ms, fl, by = read_prof(handles)                  # block1 launches of the timed region, every lane (their durations include the other lane's company)
     for h_ in handles:
@@ -916,12 +1016,12 @@ def main():
         for _ in range(5):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(window):
                 lane_step()
             torch.cuda.synchronize()
-            rep_fps.append(B * args.steps / (time.perf_counter() - t0))
+            rep_fps.append(B * window / (time.perf_counter() - t0))
             fs.drain()
-        retired.clear()
+            retired.clear()
 
     # SURVEY 8(d) side figures, each its own short pass OUTSIDE the timed region above (rank-local, per GPU)
     def rate(fn, n=5):
@@ -1000,46 +1100,18 @@ def main():
     if rank == 0 and world == 1 and not args.no_side_passes:
         side.update(side_workloads(xf, x, B))
     if rank == 0:
-        n_valid = counts[:B].tolist()
-        n_match = counts[2 * B:].tolist()
         opt_fx, opt_b1 = C.c_int(), C.c_int()
         lib.xfh_get_option(handle, b"fx", C.byref(opt_fx)); lib.xfh_get_option(handle, b"block1", C.byref(opt_b1))
         k_rows, k_sum = kernel_roofline_table(spans_us, B, B // 2, fx=opt_fx.value, block1=opt_b1.value)
         achieved = (fl / 1e12) / (ms / 1e3) if ms > 0 else 0.0
-        fps = sharding.aggregate_rate(B, args.steps, world, dt_max, "weak")
         fps_gpu = fps / world
         traffic, traffic_src = load_pmc_traffic()
         alone_us = spans_us.get(3) or (1e3 * ms / max(n_l, 1))      # block1's launch with the chip to itself (single-lane side pass); without that pass: the timed region's
+        # the box's state around the timed region (amdgpu sysfs): a slow box reads differently from a slow kernel
+        headline["config"]["gpu_state"] = {"during_the_untimed_wake_up_windows": tele_during, "before_the_wake_up": tele_before, "after_timed_region": tele_after,
+                                           "note": "before / after are single reads behind a synchronisation (an idle GPU: low sclk); `during` is sampled every 5 ms while the untimed wake-up windows run (the same steps as the timed region; a sampler inside the timed region cost it 2-4 %)"}
         out = {
-            "metric": "frames/sec detectAndCompute+match (VGA, top_k=4096)",
-            "value": round(fps, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt_max / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "VGA 640x480 sparse top_k=4096, batch=64 per GPU: detectAndCompute + MNN match of "
-                                   "the 32 consecutive frame pairs (BASELINE configs[1])",
-                       "batch_per_gpu": B, "height": H, "width": W, "top_k": TOP_K, "weights": "synthetic (tests/fixtures.py)",
-                       "arithmetic": "fp32 results; the 24-, 64- and 128-channel 3x3 convolutions, block1.2/.3 and both heads on fp16 MFMAs with an fp16 PAIR per operand "
-                                     "(x = xh + 2^-11 xl: three MFMAs per product, error <= an fp32 direct convolution's; range-guarded, the f32-MFMA / vector-ALU kernels as fallback); "
-                                     "the matcher decides on exact fp32 dot products (fp16 MFMAs only pre-select 32-wide blocks inside a derived error window)",
-                       "parallelism": f"replicas x{world}, no collective; {lanes} batches in flight per GPU (FrameStream), "
-                                      + ("a HIP stream per lane" if conc else "all lanes on one HIP stream"),
-                       "barrier": args.barrier_name,
-                       "concurrent_lanes": conc,
-                       "lanes": lanes,
-                       "untimed_before_the_timed_region": f"GPU wake-up ({n_wake} steps: windows of {args.steps} until two agree within 1 %, >= {args.wake_ms:.0f} ms; a cold GPU runs its first ~150 ms 3-4 % slow), then the W warm-up steps",
-                       "wake_up_window_fps": [round(r, 1) for r in wake_rates],
-                       # the box's state around the timed region (amdgpu sysfs): a slow box reads differently from a slow kernel
-                       "gpu_state": {"during_the_untimed_wake_up_windows": tele_during, "before_the_wake_up": tele_before, "after_timed_region": tele_after,
-                                     "note": "before / after are single reads behind a synchronisation (an idle GPU: low sclk); `during` is sampled every 5 ms while the untimed wake-up windows run (the same steps as the timed region; a sampler inside the timed region cost it 2-4 %)"},
-                       "mean_keypoints": round(float(np.mean(n_valid)), 1), "mean_matches": round(float(np.mean(n_match)), 1)},
+            **headline,
             # block1 x4 + skip1 in one kernel: fp32 FMA work on the vector ALUs (v_pk_fma_f32), LDS-tiled.  Neither HBM nor the matrix
             # cores bound it: its vector stages (conv1 recomputed inside conv2: DESIGN 3.2) do; it is priced against the dense fp32 rate of the chip,
             # which is the same 157.3 TFLOP/s for the packed vector FMA and for the f32 MFMA.  The contract's "bound" takes "hbm" | "mfma": "mfma" here names that dense

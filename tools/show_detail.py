@@ -1,4 +1,4 @@
-"""Print the headline of a bench.py run and the per-kernel rows whose name contains one of the given substrings:  python tools/show_detail.py <stdout log> <stderr log> [substring ...]"""
+"""Print the headline of a `bench.py --full` run and the per-kernel rows whose name contains one of the given substrings:  python tools/show_detail.py <stdout log> <stderr log> [substring ...]"""
 import json
 import sys
 
