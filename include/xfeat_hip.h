@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define XFH_VERSION 200          /* major*10000 + minor*100 + patch */
+#define XFH_VERSION 300          /* major*10000 + minor*100 + patch */
 
 enum {
     XFH_OK = 0,
@@ -302,6 +302,31 @@ int xfh_find_homography_matches(const float* kpts0, const float* kpts1, int kpt_
                                 const int32_t* n_matches, int P, int cap, double ransac_thr, int max_iters, double confidence, uint64_t seed,
                                 double* H, uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
 int xfh_homography_tables(double ransac_thr, uint32_t* score_table, double* weight_table, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Relative pose from the matches -- the step the evaluation takes after matching:
+ *     pose, info = poselib.estimate_relative_pose(kpts0, kpts1, cam0, cam1, {"max_epipolar_error": thr}, {})
+ * (modules/eval/megadepth1500.py, scannet1500.py), for P pairs at once.  poselib is not part of the reference tree: the
+ * algorithm is the published one (five-point essential RANSAC, Nister 2004, MSAC on the Sampson error, Gauss-Newton
+ * refinement), specified in DESIGN.md 3.10 / csrc/k_relpose.hip -- same estimate, not poselib's random stream.
+ *   pts0/pts1 (P,cap,2) fp32 pixel coordinates (device), pair p uses its first counts[p] rows (device int32; NULL: n_const
+ *   for all); K0/K1 (P,3,3) fp64 PINHOLE intrinsics (device).  All max_iters (<= 16384; larger is an error) hypotheses are
+ *   scored on the device, the stopping rule (min_iters, success_prob) applied to the cost list afterwards.
+ *   R (P,9) fp64 row-major, t (P,3) fp64 unit norm, E = [t]x R (P,9); mask (P,cap) uint8, 1 = Sampson error below the
+ *   threshold; info (P,8) int32: found, winning hypothesis, hypotheses the loop would have run, inliers, accepted refinement
+ *   steps, n, cost (lo, hi word).  Fewer than 5 correspondences / inliers: found = 0 and zeros in R, t, E and the mask.
+ *   xfh_estimate_relpose_matches: the same on the matcher's output (kpts + idx0/idx1 + n_matches), as for the homography.
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_relpose_workspace_bytes(int P, int max_iters);
+int xfh_estimate_relpose(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap,
+                         const double* K0, const double* K1, double max_epipolar_error, int min_iters, int max_iters,
+                         double success_prob, uint64_t seed, double* R, double* t, double* E, uint8_t* mask, int32_t* info,
+                         void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_estimate_relpose_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                                 const int32_t* n_matches, int P, int cap, const double* K0, const double* K1,
+                                 double max_epipolar_error, int min_iters, int max_iters, double success_prob, uint64_t seed,
+                                 double* R, double* t, double* E, uint8_t* mask, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * LighterGlue: the attention matcher of XFeat.match_lighterglue (modules/xfeat.py:131-162), i.e.

@@ -1,0 +1,151 @@
+"""The relative-pose restatement (tests/pose_reference.py) against ground truth, and the evaluation metrics of accelerated_features_amd.pose
+on hand-computed cases.  CPU only: the restatement is what the GPU tests hold the kernels to, so it is checked here on its own."""
+import os
+
+import numpy as np
+import pytest
+
+import pose_reference as PR
+from accelerated_features_amd.pose import pose_auc, relative_pose_error
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+POSES = os.path.join(HERE, "golden", "megadepth1500_poses.npz")
+
+
+def _rot(w):
+    th = np.linalg.norm(w)
+    k = w / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+def _samples(rng, H):
+    x = np.zeros((4, H, 5))
+    gt = []
+    for h in range(H):
+        R, t = _rot(rng.normal(size=3) * 0.3), rng.normal(size=3)
+        t /= np.linalg.norm(t)
+        X = np.c_[rng.uniform(-1, 1, (5, 2)), rng.uniform(2, 6, 5)]
+        X2 = X @ R.T + t
+        x[0, h], x[1, h], x[2, h], x[3, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2], X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
+        gt.append((R, t))
+    return x, gt
+
+
+def test_every_candidate_is_an_essential_matrix_through_the_sample():
+    rng = np.random.default_rng(0)
+    x, _ = _samples(rng, 1000)
+    x[:, 500:] = rng.uniform(-0.7, 0.7, (4, 500, 5))          # half of them random (no true motion)
+    cand, nc = PR.solve(*x)
+    assert (nc[:500] > 0).mean() >= 0.999                       # a true motion leaves its candidate
+    res = []
+    for h in range(1000):
+        for c in range(nc[h]):
+            R, t = cand[h, c, :9].reshape(3, 3), cand[h, c, 9:]
+            E = PR.essential_from_pose(R, t)
+            s = np.linalg.norm(E)
+            x1 = np.c_[x[0, h], x[1, h], np.ones(5)]
+            x2 = np.c_[x[2, h], x[3, h], np.ones(5)]
+            epi = np.abs(np.einsum("ij,jk,ik->i", x2, E, x1)) / (s * np.linalg.norm(x1, axis=1) * np.linalg.norm(x2, axis=1))
+            det = abs(np.linalg.det(E)) / s ** 3
+            trc = np.abs(2 * E @ E.T @ E - np.trace(E @ E.T) * E).max() / s ** 3
+            orth = np.abs(R @ R.T - np.eye(3)).max()
+            assert np.linalg.det(R) > 0 and abs(np.linalg.norm(t) - 1.0) <= 1e-12
+            res.append(max(epi.max(), det, trc, orth))
+    res = np.array(res)
+    # relative residuals of every candidate (epipolar equations, det E, the trace constraint, R R' - I).  Measured on 4000 scene samples:
+    # 98 % of the candidates at <= 1e-10, 99.6 % at <= 1e-8, none above 1e-2.  The few above 1e-10 are roots of a degree-10 polynomial that is
+    # ill-conditioned there (more bisection or Newton steps leave them where they are: the limit is the polynomial's coefficients).
+    assert (res <= 1e-10).mean() >= 0.97, np.sort(res)[-20:]
+    assert (res <= 1e-8).mean() >= 0.99
+    assert res.max() <= 1e-1
+
+
+def test_ground_truth_pose_is_among_the_candidates():
+    rng = np.random.default_rng(1)
+    x, gt = _samples(rng, 2000)
+    cand, nc = PR.solve(*x)
+    best = np.array([min([np.abs(cand[h, c, :9] - gt[h][0].ravel()).max() + np.abs(cand[h, c, 9:] - gt[h][1]).max() for c in range(nc[h])] or [9.0])
+                     for h in range(len(gt))])
+    # measured on 4000 noise-free samples: 99.9 % within 1e-6 of the true (R, t), 97.3 % within 1e-10 (with the null basis orthonormalised;
+    # without it 91 % / 98 % at 1e-6 / 1e-2)
+    assert (best <= 1e-6).mean() >= 0.995, np.sort(best)[-20:]
+    assert (best <= 1e-10).mean() >= 0.95
+
+
+def test_decomposition_returns_the_pose_that_puts_points_in_front():
+    rng = np.random.default_rng(2)
+    x, gt = _samples(rng, 200)
+    cand, nc = PR.solve(*x)
+    for h in range(200):
+        for c in range(nc[h]):
+            R, t = cand[h, c, :9].reshape(3, 3), cand[h, c, 9:]
+            x1 = np.c_[x[0, h], x[1, h], np.ones(5)]
+            x2 = np.c_[x[2, h], x[3, h], np.ones(5)]
+            for i in range(5):               # depths by least squares: d1 R x1 - d2 x2 = -t
+                d = np.linalg.lstsq(np.c_[R @ x1[i], -x2[i]], -t, rcond=None)[0]
+                assert (d > 0).all()
+
+
+def test_relative_pose_error_hand_cases():
+    T = np.eye(4)
+    T[:3, 3] = [1.0, 0.0, 0.0]
+    assert relative_pose_error(T, np.eye(3), [1.0, 0.0, 0.0]) == (0.0, 0.0)
+    assert relative_pose_error(T, np.eye(3), [-2.0, 0.0, 0.0])[0] == 0.0                  # the sign of t is not observable
+    te, re = relative_pose_error(T, _rot(np.array([0.0, 0.0, np.deg2rad(10.0)])), [1.0, 1.0, 0.0])
+    assert abs(te - 45.0) < 1e-9 and abs(re - 10.0) < 1e-9
+    te, _ = relative_pose_error(T, np.eye(3), [0.0, 1.0, 0.0])
+    assert abs(te - 90.0) < 1e-9
+    T[:3, 3] = 0.0
+    assert relative_pose_error(T, np.eye(3), [0.0, 1.0, 0.0], ignore_gt_t_thr=0.5)[0] == 0.0
+
+
+def test_pose_auc_hand_cases():
+    # errors 0, 0 -> recall 1 from the start: AUC 1 at every threshold
+    assert pose_auc([0.0, 0.0], (5,)) == {"auc@5": 1.0}
+    # one error of 2 degrees, one above: curve (0,0) -> (2,0.5), held to 5 -> area 0.5 * 2 * 0.5 + 3 * 0.5 = 2.0 -> 0.4
+    assert abs(pose_auc([2.0, 50.0], (5,))["auc@5"] - 0.4) < 1e-12
+    # all errors above the threshold
+    assert pose_auc([30.0, np.inf], (5, 10, 20)) == {"auc@5": 0.0, "auc@10": 0.0, "auc@20": 0.0}
+    # errors 1, 3 at threshold 4: (0,0)-(1,.5): .25 ; (1,.5)-(3,1): 1.5 ; (3,1)-(4,1): 1 -> 2.75 / 4
+    assert abs(pose_auc([3.0, 1.0], (4,))["auc@4"] - 2.75 / 4) < 1e-12
+
+
+@pytest.mark.parametrize("outliers", [0.0, 0.3, 0.6])
+def test_estimator_recovers_fixture_poses(outliers):
+    f = dict(np.load(POSES))
+    rng = np.random.default_rng(int(outliers * 10))
+    errs = []
+    for p in range(0, 1500, 150):
+        a, b, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 600, 0.7, outliers, tuple(f["size0_hw"][p]), tuple(f["size1_hw"][p]), rng)
+        r = PR.estimate(a, b, f["K0"][p], f["K1"][p], 1.0, max_iterations=2000, seed=3, pair=p)
+        assert r["info"][0] == 1
+        assert abs(np.linalg.norm(r["t"]) - 1.0) < 1e-12
+        assert np.allclose(r["E"], PR.essential_from_pose(r["R"], r["t"]), atol=1e-15)
+        errs.append(max(relative_pose_error(f["T_0to1"][p], r["R"], r["t"])))
+    # thresholds from this run with a margin (median 0.1-0.3 degrees, worst 1-2 degrees on these poses)
+    assert np.median(errs) < 1.0 and max(errs) < 5.0, errs
+
+
+def test_estimator_degenerate_inputs():
+    K = np.array([[800.0, 0, 320], [0, 800.0, 240], [0, 0, 1]])
+    r = PR.estimate(np.zeros((4, 2), np.float32), np.zeros((4, 2), np.float32), K, K)
+    assert list(r["info"]) == [0, -1, 0, 0, 0, 4, 0, 0] and not r["mask"].any()
+    same = np.full((50, 2), 100.0, np.float32)
+    r = PR.estimate(same, same, K, K, max_iterations=300)
+    assert r["info"][0] == 0 and r["info"][1] == -1 and np.isfinite(r["R"]).all()
+
+
+def test_megadepth_synthetic_auc_on_every_10th_pair():
+    """Where the GPU test's AUC floors come from: the restatement on every 10th pair of the same synthetic set clears them with margin."""
+    f = dict(np.load(POSES))
+    pts0, pts1, counts = PR.megadepth_synthetic(f)
+    err = []
+    for p in range(0, 1500, 10):
+        n = counts[p]
+        r = PR.estimate(pts0[p, :n], pts1[p, :n], f["K0"][p], f["K1"][p], 1.0, max_iterations=1000, seed=0, pair=p)
+        err.append(max(relative_pose_error(f["T_0to1"][p], r["R"], r["t"])) if r["info"][0] else np.inf)
+    auc = pose_auc(err)
+    print("restatement, every 10th pair:", auc)
+    for k, v in PR.AUC_FLOORS.items():
+        assert auc[k] >= v + 0.02, (k, auc)
