@@ -1,6 +1,7 @@
 // Host emulation of the few GPU facilities a kernel body of csrc/ needs (tests/emu/*.cpp): one host thread per work-item, a workgroup at a time.
 // LDS is a buffer, __syncthreads a barrier over the workgroup's threads, the LDS-DMA a copy, v_mfma_f32_16x16x32_f16 an exchange among the 64 threads of a wave
 // (exact fp16 products, the accumulator rounded to fp32 once per instruction: what tests/test_block1_fx_model.py assumes of the instruction).
+// __builtin_amdgcn_exp2f is raw v_exp_f32: results below 2^-126 flush to 0 (no denormals), unlike exp2f().  __any / __ballot are wave-wide, through the wave barrier.
 // Not a model of timing or of memory ordering: it checks index arithmetic, tile layouts and the barrier structure (a missing barrier usually shows as a wrong
 // result here too, since the host threads run at very different paces).
 #pragma once
@@ -147,6 +148,31 @@ inline double shfl_xor(double v, int mask) {      // (a thread's exchange slot i
     wg->wave_bar[w]->arrive_and_wait();
     return r;
 }
+inline unsigned shfl_xor(unsigned v, int mask) {
+    const int t = tidx.x, w = t >> 6, l = t & 63;
+    std::memcpy(&wg->opa32[t * 8], &v, 4);
+    wg->wave_bar[w]->arrive_and_wait();
+    unsigned r;
+    std::memcpy(&r, &wg->opa32[(w * 64 + (l ^ mask)) * 8], 4);
+    wg->wave_bar[w]->arrive_and_wait();
+    return r;
+}
+inline int shfl_xor(int v, int mask) { return (int)shfl_xor((unsigned)v, mask); }
+// __ballot / __any: every lane's predicate through the wave barrier, as shfl_xor does
+inline unsigned long long ballot(bool p) {
+    const int t = tidx.x, w = t >> 6;
+    wg->opa32[t * 8] = p ? 1.f : 0.f;
+    wg->wave_bar[w]->arrive_and_wait();
+    unsigned long long r = 0;
+    for (int l = 0; l < 64; ++l) if (wg->opa32[(w * 64 + l) * 8] != 0.f) r |= 1ull << l;
+    wg->wave_bar[w]->arrive_and_wait();
+    return r;
+}
+// v_exp_f32 (__builtin_amdgcn_exp2f): no denormal results -- anything below 2^-126 flushes to 0 (exp2f() proper would return the denormal)
+inline float exp2_raw(float x) {
+    const float r = std::exp2(x);
+    return r < 0x1p-126f ? 0.f : r;
+}
 inline void dma(const void* g, void* l_base, int size) { std::memcpy(static_cast<unsigned char*>(l_base) + size * (tidx.x & 63), g, size); }      // (M0 base + lane x size)
 struct Rsrc { unsigned char* base; unsigned bytes; };
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -264,6 +290,10 @@ typedef emu::Rsrc __amdgpu_buffer_rsrc_t;
 #define __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, x, y, z) emu::mfma32x2(a, b, c)
 #define __builtin_amdgcn_sched_group_barrier(mask, n, id) ((void)0)
 #define __shfl_xor(v, mask, width) emu::shfl_xor(v, mask)
+#define __ballot(p) emu::ballot(p)
+#define __any(p) (emu::ballot(p) != 0ull)
+#define __popcll(v) __builtin_popcountll(v)
+#define __builtin_amdgcn_exp2f(x) emu::exp2_raw(x)
 #define __builtin_amdgcn_global_load_lds(g, l, size, off, aux) emu::dma(g, l, size)
 #define __builtin_amdgcn_make_buffer_rsrc(p, stride, bytes, flags) emu::Rsrc{reinterpret_cast<unsigned char*>(p), (unsigned)(bytes)}
 #define __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, aux) emu::buffer_load_b128(rs, (unsigned)(voff), (unsigned)(soff))

@@ -129,7 +129,11 @@ def star_pair(B, H, W, seed=41, noise=0.005):
 # LighterGlue: synthetic weights in the key layout kornia's LightGlue has after the reference's loader
 # (modules/lighterglue.py:41-48); the trained xfeat-lighterglue.pt is not in the snapshot.
 # ------------------------------------------------------------------------------------------------------------
-def lighterglue_state_dict(seed=0):
+def lighterglue_state_dict(seed=0, qk_gain=1.0, match_bias=None):
+    """Defaults: the fixture of every test.  Variants (the default draws are unchanged; the variant scales or replaces some of them afterwards):
+    qk_gain   multiplies the q and k rows of every self_attn.Wqkv (weight and bias) and the whole cross_attn.to_qk, so attention logits grow by qk_gain^2:
+              peaked softmaxes, as trained weights give;
+    match_bias replaces every log_assignment.*.matchability.bias: strongly negative values prune most of a set after each layer."""
     import numpy as np
     import torch
     from oracle.lighterglue_oracle import state_dict_keys
@@ -151,6 +155,17 @@ def lighterglue_state_dict(seed=0):
         else:                                                   # Linear weights (out, in)
             v = rs.randn(*shape) * (1.0 / np.sqrt(shape[-1]))
         sd[name] = torch.from_numpy(v.astype(np.float32))
+    if qk_gain != 1.0:
+        g = np.float32(qk_gain)
+        for name in list(sd):
+            if ".self_attn.Wqkv." in name:          # output feature 3c + t is component c of (q, k, v)[t]
+                sd[name][(torch.arange(sd[name].shape[0]) % 3) < 2] *= g
+            elif ".cross_attn.to_qk." in name:
+                sd[name] *= g
+    if match_bias is not None:
+        for name in sd:
+            if name.endswith("matchability.bias"):
+                sd[name].fill_(float(match_bias))
     return sd
 
 
