@@ -913,6 +913,45 @@ int xfh_estimate_relpose_matches(const float* kpts0, const float* kpts1, int kpt
                                  min_iters, max_iters, success_prob, seed, R, t, E, mask, info, workspace, workspace_bytes, stream);
 }
 
+size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
+    if (P <= 0 || max_iters <= 0) return 0;
+    return xfh::fundamental_workspace_bytes(P, max_iters);
+}
+
+static int find_fundamental_impl(const char* who, const float* pts0, const float* pts1, const int64_t* idx0, const int64_t* idx1, int kcap,
+                                 const int32_t* counts, int n_const, int P, int cap, int method, double ransac_thr, int max_iters,
+                                 double confidence, uint64_t seed, double* F, uint8_t* mask, int32_t* info, void* workspace,
+                                 size_t workspace_bytes, xfh_stream stream) {
+    if (!pts0 || !pts1 || !F || !mask || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (P <= 0 || P > 65535 || cap <= 0 || cap > (1 << 24) || kcap <= 0 || (!counts && (n_const < 0 || n_const > cap)))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, n %d)", who, P, cap, n_const);
+    if (method != XFH_FM_7POINT && method != XFH_FM_8POINT && method != XFH_FM_USAC_MAGSAC)
+        return fail(XFH_ERR_UNSUPPORTED, "%s: method %d (supported: FM_7POINT 1, FM_8POINT 2, USAC_MAGSAC 38)", who, method);
+    if (!(ransac_thr > 0.0) || !(confidence > 0.0 && confidence < 1.0)) return fail(XFH_ERR_ARG, "%s: threshold %g / confidence %g", who, ransac_thr, confidence);
+    if (max_iters < 1 || max_iters > 16384) return fail(XFH_ERR_UNSUPPORTED, "%s: max_iters %d outside [1, 16384]", who, max_iters);
+    int rc = check_ws(workspace, workspace_bytes, xfh::fundamental_workspace_bytes(P, max_iters));
+    if (rc) return rc;
+    if (launch_find_fundamental(pts0, pts1, idx0, idx1, kcap, counts, n_const, P, cap, method, ransac_thr, max_iters, confidence, seed, F, mask, info,
+                                workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: unsupported configuration", who);
+    return check_launch(who);
+}
+
+int xfh_find_fundamental(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap, int method, double ransac_thr,
+                         int max_iters, double confidence, uint64_t seed, double* F, uint8_t* mask, int32_t* info, void* workspace,
+                         size_t workspace_bytes, xfh_stream stream) {
+    return find_fundamental_impl("xfh_find_fundamental", pts0, pts1, nullptr, nullptr, cap, counts, n_const, P, cap, method, ransac_thr, max_iters,
+                                 confidence, seed, F, mask, info, workspace, workspace_bytes, stream);
+}
+
+int xfh_find_fundamental_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                                 const int32_t* n_matches, int P, int cap, int method, double ransac_thr, int max_iters, double confidence,
+                                 uint64_t seed, double* F, uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    if (!idx0 || !idx1 || !n_matches) return fail(XFH_ERR_ARG, "xfh_find_fundamental_matches: NULL argument");
+    return find_fundamental_impl("xfh_find_fundamental_matches", kpts0, kpts1, idx0, idx1, kpt_cap, n_matches, 0, P, cap, method, ransac_thr,
+                                 max_iters, confidence, seed, F, mask, info, workspace, workspace_bytes, stream);
+}
+
 int xfh_kpts_heatmap(const float* logits, int B, int hc, int wc, float* heat, xfh_stream stream) {
     if (!logits || !heat || B <= 0 || hc <= 0 || wc <= 0) return fail(XFH_ERR_ARG, "xfh_kpts_heatmap: bad argument");
     launch_softmax_heat(logits, B, hc, wc, heat, (hipStream_t)stream);

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define XFH_VERSION 300          /* major*10000 + minor*100 + patch */
+#define XFH_VERSION 301          /* major*10000 + minor*100 + patch */
 
 enum {
     XFH_OK = 0,
@@ -326,6 +326,34 @@ int xfh_estimate_relpose_matches(const float* kpts0, const float* kpts1, int kpt
                                  const int32_t* n_matches, int P, int cap, const double* K0, const double* K1,
                                  double max_epipolar_error, int min_iters, int max_iters, double success_prob, uint64_t seed,
                                  double* R, double* t, double* E, uint8_t* mask, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
+ *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
+ * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
+ * (7-point RANSAC with the oriented epipolar constraint, MAGSAC++ quality and sigma-consensus++ re-weighted 8-point
+ * refinement) as specified in DESIGN.md 3.11 / csrc/k_fundamental.hip -- same estimate, not OpenCV's random stream.
+ *   pts0/pts1 (P,cap,2) fp32 pixel coordinates (device), pair p uses its first counts[p] rows (device int32; NULL: n_const
+ *   for all).  method XFH_FM_USAC_MAGSAC: all max_iters (<= 16384; larger is an error) hypotheses are scored on the device,
+ *   the stopping rule (confidence) applied to the score list afterwards; XFH_FM_8POINT: one least-squares 8-point fit on
+ *   all n >= 8 points; XFH_FM_7POINT: the 7-point solver on exactly 7 points, every real root.
+ *   F (P,3,9) fp64 row-major, model m of pair p at F[p][m]: one model (m = 0) except for XFH_FM_7POINT (up to 3); scaled to
+ *   F[8] = 1 when |F[8]| > FLT_EPSILON after normalising to unit Frobenius norm; zeros where there is no model.
+ *   mask (P,cap) uint8, 1 = Sampson error < ransac_thr (pixels) under the final F (non-robust methods: 1 for every point
+ *   used); info (P,8) int32: found, winning hypothesis (-1: none / non-robust), hypotheses the loop would have run (non-robust:
+ *   the number of models), inliers, accepted refinement steps, n, quality (lo, hi word).  found = 0 with fewer than 7
+ *   inliers (cv2 returns None).  xfh_find_fundamental_matches: the same on the matcher's output (kpts + idx0/idx1 +
+ *   n_matches), as for the homography.
+ * ---------------------------------------------------------------------------------------- */
+enum { XFH_FM_7POINT = 1, XFH_FM_8POINT = 2, XFH_FM_USAC_MAGSAC = 38 };
+size_t xfh_fundamental_workspace_bytes(int P, int max_iters);
+int xfh_find_fundamental(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap, int method,
+                         double ransac_thr, int max_iters, double confidence, uint64_t seed,
+                         double* F, uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_find_fundamental_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                                 const int32_t* n_matches, int P, int cap, int method, double ransac_thr, int max_iters,
+                                 double confidence, uint64_t seed, double* F, uint8_t* mask, int32_t* info,
                                  void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,0 +1,508 @@
+"""float64 numpy restatement of the fundamental-matrix estimator of csrc/k_fundamental.hip: Hartley conditioning,
+7-point RANSAC with the oriented epipolar constraint, the MAGSAC++ quality on the Sampson error, the sequential loop's stopping rule,
+re-weighted 8-point refinement of the winner; and the non-robust FM_7POINT / FM_8POINT modes.
+
+It performs the kernel's operations in the kernel's order (numpy never fuses a multiply and an add, and every product and sum here is
+rounded once, as in the kernel's file with fp contraction off), vectorised over hypotheses, so its results are comparable bit for bit:
+the candidates of a sample (``solve``), the integer qualities, the winner, the iteration count, the mask and -- because the refinement's
+sums are formed in the select kernel's fixed block order and its Jacobi sweeps are repeated rotation for rotation -- the refined F.
+The one function outside + - * / sqrt is the bound's log, as in the kernel.  The MAGSAC++ tables are the homography's: pass the ones
+the device computed (``xfh_homography_tables``) to compare with the kernels; by default they come from oracle/homography_oracle.py,
+whose quality table equals the device's and whose weights agree to 1e-12.
+"""
+import math
+
+import numpy as np
+
+import pose_reference as PR
+
+MAX_DRAWS, LO_ITERS, MAX_ITERS, MAX_CAND, NBINS = 16, 5, 16384, 3, 4096
+BISECT_STEPS, NEWTON_STEPS, JACOBI_SWEEPS = 64, 3, 10
+PIVOT_EPS = 1e-12
+FLT_EPS = 1.1920928955078125e-07
+FIT_RANK_EPS = 1e-12
+MAX_THR_FACTOR = 2.0
+FM_7POINT, FM_8POINT, USAC_MAGSAC = 1, 2, 38
+SQRT2 = 1.41421356237309504880
+GOLDEN = np.uint64(0x9e3779b97f4a7c15)
+
+
+def tables(thr):
+    """(bin_scale, quality table uint32[4096], weight table float64[4096]) of threshold thr (oracle/homography_oracle.py)."""
+    from oracle import homography_oracle as HO
+    return HO.tables(thr)
+
+
+def bin_scale_of(thr):
+    t_max = MAX_THR_FACTOR * float(thr)
+    return NBINS / (t_max * t_max)
+
+
+# ---- small helpers ---------------------------------------------------------------------------------------------------------------------------
+finite, cross, dot, pmul = PR.finite, PR.cross, PR.dot, PR.pmul
+
+
+def sampson(F, a, b, c, d):
+    e0 = (F[0] * a + F[1] * b) + F[2]
+    e1 = (F[3] * a + F[4] * b) + F[5]
+    e2 = (F[6] * a + F[7] * b) + F[8]
+    f0 = (F[0] * c + F[3] * d) + F[6]
+    f1 = (F[1] * c + F[4] * d) + F[7]
+    num = (c * e0 + d * e1) + e2
+    den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1
+    return num * num / den
+
+
+def cubic(a, x):
+    return ((x + a[2]) * x + a[1]) * x + a[0]
+
+
+def dcubic(a, b2, x):
+    return (3.0 * x + b2) * x + a[1]
+
+
+def cubic_roots(a):
+    """Real roots of the monic cubics x^3 + a2 x^2 + a1 x + a0 (a: 3 arrays (H,)), the kernel's brackets / bisection / Newton.
+    Returns roots (H, 3) (ascending in the first `nr` slots, 0 elsewhere) and nr (H,)."""
+    a = [np.asarray(v, np.float64) for v in a]
+    H = a[0].shape[0]
+    with np.errstate(all="ignore"):
+        bound = np.abs(a[0])
+        bound = np.where(np.abs(a[1]) > bound, np.abs(a[1]), bound)
+        bound = np.where(np.abs(a[2]) > bound, np.abs(a[2]), bound)
+        bound = 1.0 + bound
+        ok = finite(bound)
+        disc = a[2] * a[2] - 3.0 * a[1]
+        sq = np.sqrt(np.where(disc > 0.0, disc, 0.0))
+        e = [-bound, np.where(disc > 0.0, (-a[2] - sq) / 3.0, bound), np.where(disc > 0.0, (-a[2] + sq) / 3.0, bound), bound]
+        b2 = 2.0 * a[2]
+        roots = np.zeros((H, 3))
+        nr = np.zeros(H, np.int64)
+        for j in range(3):
+            lo, hi = e[j].copy(), e[j + 1].copy()
+            flo, fhi = cubic(a, lo), cubic(a, hi)
+            has = ok & ((flo > 0.0) != (fhi > 0.0))
+            slo = flo > 0.0
+            for _ in range(BISECT_STEPS):
+                mid = 0.5 * (lo + hi)
+                c = (cubic(a, mid) > 0.0) == slo
+                lo = np.where(c, mid, lo)
+                hi = np.where(c, hi, mid)
+            z = 0.5 * (lo + hi)
+            for _ in range(NEWTON_STEPS):
+                f, df = cubic(a, z), dcubic(a, b2, z)
+                zn = z - f / df
+                z = np.where(np.abs(cubic(a, zn)) < np.abs(f), zn, z)
+            for k in range(3):
+                roots[:, k] = np.where(has & (nr == k), z, roots[:, k])
+            nr += has
+    return roots, nr
+
+
+def denormalise(Fn, nt):
+    """Fp = T1' Fn T0; Fn a list of 9 arrays, nt = (cx0, cy0, s0, cx1, cy1, s1) (scalars or arrays)."""
+    cx0, cy0, s0, cx1, cy1, s1 = nt
+    tx0, ty0, tx1, ty1 = s0 * cx0, s0 * cy0, s1 * cx1, s1 * cy1
+    G = [None] * 9
+    for i in range(3):
+        G[3 * i] = Fn[3 * i] * s0
+        G[3 * i + 1] = Fn[3 * i + 1] * s0
+        G[3 * i + 2] = Fn[3 * i + 2] - (Fn[3 * i] * tx0 + Fn[3 * i + 1] * ty0)
+    Fp = [None] * 9
+    for j in range(3):
+        Fp[j] = s1 * G[j]
+        Fp[3 + j] = s1 * G[3 + j]
+        Fp[6 + j] = G[6 + j] - (tx1 * G[j] + ty1 * G[3 + j])
+    return Fp
+
+
+# ---- the minimal solver -------------------------------------------------------------------------------------------------------------------
+def solve(x0, y0, x1, y1, nt, oriented=True):
+    """Candidate F (pixels) of H 7-point samples: x0 .. y1 (H, 7) normalised coordinates, nt the pair's conditioning (6 scalars, or 6
+    arrays (H,)).  Returns (cand (H, 3, 9), ncand (H,)); `roots` of the cubic are not returned (see solve_cubic)."""
+    x0, y0, x1, y1 = (np.asarray(v, np.float64) for v in (x0, y0, x1, y1))
+    H = x0.shape[0]
+    nt = [np.asarray(v, np.float64)[:, None] if np.ndim(v) else float(v) for v in nt]
+    with np.errstate(all="ignore"):
+        A = np.zeros((H, 7, 9))
+        for k in range(7):
+            a, b, c, d = x0[:, k], y0[:, k], x1[:, k], y1[:, k]
+            for j, v in enumerate((c * a, c * b, c, d * a, d * b, d, a, b, 1.0)):
+                A[:, k, j] = v
+        ok = PR.gauss_jordan(A)
+        f2, D = [], []
+        for m in range(9):
+            v1 = -A[:, m, 7] if m < 7 else np.full(H, 1.0 if m == 7 else 0.0)
+            v2 = -A[:, m, 8] if m < 7 else np.full(H, 1.0 if m == 8 else 0.0)
+            f2.append(v2)
+            D.append(v1 - v2)
+        c = solve_cubic(f2, D)
+        lead = c[3]
+        ok &= (np.abs(lead) > 0.0) & finite(lead)
+        a = [c[0] / lead, c[1] / lead, c[2] / lead]
+        roots, nr = cubic_roots(a)
+        valid = ok[:, None] & (np.arange(3)[None, :] < nr[:, None])
+        z = roots
+        Fn = [f2[m][:, None] + z * D[m][:, None] for m in range(9)]
+        for m in range(9):
+            valid &= finite(Fn[m])
+        if oriented:
+            k0, k1, k2 = [Fn[0], Fn[3], Fn[6]], [Fn[1], Fn[4], Fn[7]], [Fn[2], Fn[5], Fn[8]]
+            c01, c02, c12 = cross(k0, k1), cross(k0, k2), cross(k1, k2)
+            n01, n02, n12 = dot(c01, c01), dot(c02, c02), dot(c12, c12)
+            mx = np.where(n02 > n01, n02, n01)
+            tp = np.where(n12 > mx, 2, np.where(n02 > n01, 1, 0))
+            ne = np.where(tp == 0, n01, np.where(tp == 1, n02, n12))
+            ep = [np.where(tp == 0, c01[k], np.where(tp == 1, c02[k], c12[k])) for k in range(3)]
+            valid &= ne > 0.0
+            pos = np.zeros(z.shape, np.int64)
+            neg = np.zeros(z.shape, np.int64)
+            for i in range(7):
+                xa, xb = x0[:, i][:, None], y0[:, i][:, None]
+                p1 = [x1[:, i][:, None], y1[:, i][:, None], 1.0]
+                fx = [(Fn[0] * xa + Fn[1] * xb) + Fn[2], (Fn[3] * xa + Fn[4] * xb) + Fn[5], (Fn[6] * xa + Fn[7] * xb) + Fn[8]]
+                v = dot(cross(ep, p1), fx)
+                pos += v > 0.0
+                neg += v < 0.0
+            valid &= (pos == 7) | (neg == 7)
+        Fp = denormalise(Fn, nt)
+        for m in range(9):
+            valid &= finite(Fp[m])
+        Fs = np.stack([np.broadcast_to(v, z.shape) for v in Fp], axis=-1)          # (H, 3, 9)
+    ncand = valid.sum(axis=1)
+    slot = np.cumsum(valid, axis=1) - 1
+    cand = np.zeros((H, MAX_CAND, 9))
+    hi_, ki_ = np.nonzero(valid)
+    cand[hi_, slot[hi_, ki_]] = Fs[hi_, ki_]
+    return cand, ncand
+
+
+def solve_cubic(f2, D):
+    """Coefficients c0..c3 (ascending) of det(F2 + a D), the kernel's products in the kernel's order."""
+    m = [[f2[i], D[i]] for i in range(9)]
+    sub = lambda p, q: [p[k] - q[k] for k in range(len(p))]            # noqa: E731
+    q0 = sub(pmul(m[4], m[8]), pmul(m[5], m[7]))
+    q1 = sub(pmul(m[3], m[8]), pmul(m[5], m[6]))
+    q2 = sub(pmul(m[3], m[7]), pmul(m[4], m[6]))
+    c = pmul(m[0], q0)
+    c = sub(c, pmul(m[1], q1))
+    w = pmul(m[2], q2)
+    return [c[k] + w[k] for k in range(4)]
+
+
+# ---- refinement: Jacobi, 8-point fit, output scaling (scalar, the kernel's order) ------------------------------------------------------
+def jacobi(A, N):
+    """Cyclic Jacobi on the symmetric N x N matrix A (list of N*N floats, both triangles, modified in place); returns V (N*N)."""
+    V = [1.0 if i == j else 0.0 for i in range(N) for j in range(N)]
+    for _ in range(JACOBI_SWEEPS):
+        for p in range(N - 1):
+            for q in range(p + 1, N):
+                apq = A[p * N + q]
+                if apq == 0.0:
+                    continue
+                app, aqq = A[p * N + p], A[q * N + q]
+                theta = _div(aqq - app, 2.0 * apq)
+                r = _sqrt(theta * theta + 1.0)
+                t = _div(1.0, theta + r) if theta >= 0.0 else -_div(1.0, r - theta)
+                c = _div(1.0, _sqrt(t * t + 1.0))
+                sn = t * c
+                for k in range(N):
+                    if k == p or k == q:
+                        continue
+                    akp, akq = A[k * N + p], A[k * N + q]
+                    np_, nq = c * akp - sn * akq, sn * akp + c * akq
+                    A[k * N + p] = A[p * N + k] = np_
+                    A[k * N + q] = A[q * N + k] = nq
+                A[p * N + p] = app - t * apq
+                A[q * N + q] = aqq + t * apq
+                A[p * N + q] = A[q * N + p] = 0.0
+                for k in range(N):
+                    vkp, vkq = V[k * N + p], V[k * N + q]
+                    V[k * N + p] = c * vkp - sn * vkq
+                    V[k * N + q] = sn * vkp + c * vkq
+    return V
+
+
+def _div(a, b):
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def _sqrt(x):
+    with np.errstate(all="ignore"):
+        return float(np.sqrt(np.float64(x)))
+
+
+def _smallest(A, N):
+    m = 0
+    for k in range(1, N):
+        if A[k * N + k] < A[m * N + m]:
+            m = k
+    return m
+
+
+def fit8(sm, nt):
+    """The 8-point fit from the 45 sums; returns F in pixels (list of 9), or None when the normal matrix has rank below 8 or F is not finite."""
+    sm = [float(v) for v in sm]
+    A = [0.0] * 81
+    k = 0
+    for i in range(9):
+        for j in range(i, 9):
+            A[9 * i + j] = A[9 * j + i] = sm[k]
+            k += 1
+    V = jacobi(A, 9)
+    m = _smallest(A, 9)
+    l2, lmax, first = 0.0, 0.0, True
+    for i in range(9):
+        d = A[9 * i + i]
+        lmax = d if d > lmax else lmax
+        if i != m and (first or d < l2):
+            l2, first = d, False
+    if not l2 > FIT_RANK_EPS * lmax:
+        return None
+    Fn = [V[9 * i + m] for i in range(9)]
+    B = [(Fn[i] * Fn[j] + Fn[3 + i] * Fn[3 + j]) + Fn[6 + i] * Fn[6 + j] for i in range(3) for j in range(3)]
+    W = jacobi(B, 3)
+    m = _smallest(B, 3)
+    v = [W[m], W[3 + m], W[6 + m]]
+    for i in range(3):
+        u = (Fn[3 * i] * v[0] + Fn[3 * i + 1] * v[1]) + Fn[3 * i + 2] * v[2]
+        for j in range(3):
+            Fn[3 * i + j] = Fn[3 * i + j] - u * v[j]
+    Fp = [float(x) for x in denormalise([np.float64(x) for x in Fn], [np.float64(x) for x in nt])]
+    if not all(math.isfinite(x) for x in Fp):
+        return None
+    return Fp
+
+
+def scale_out(F):
+    with np.errstate(all="ignore"):
+        F = np.asarray(F, np.float64)
+        nn = np.float64(0.0)
+        for k in range(9):
+            nn = nn + F[k] * F[k]
+        g = F / np.sqrt(nn)
+        return g / g[8] if abs(g[8]) > FLT_EPS else g
+
+
+# ---- sampling, conditioning, the estimator ----------------------------------------------------------------------------------------------
+def draws(seed, pair, its, n):
+    """Sample indices (H, 7) and ok (H,) of hypotheses `its` of pair `pair` with n correspondences."""
+    its = np.asarray(its, np.uint64)
+    H = its.shape[0]
+    idx = np.full((H, 7), -1, np.int64)
+    slot = np.zeros(H, np.int64)
+    with np.errstate(over="ignore"):
+        for d in range(MAX_DRAWS):
+            counter = (np.uint64(pair) * np.uint64(1 << 20) + its) * np.uint64(MAX_DRAWS) + np.uint64(d)
+            h = PR.mix64(np.uint64(seed) + GOLDEN * (counter + np.uint64(1)))
+            c = (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+            dup = np.zeros(H, bool)
+            for k in range(6):
+                dup |= (slot > k) & (c == idx[:, k])
+            take = (slot < 7) & ~dup
+            for k in range(7):
+                idx[:, k] = np.where(take & (slot == k), c, idx[:, k])
+            slot += take
+    return idx, slot >= 7
+
+
+def conditioning(P0, P1):
+    """The prep kernel's Hartley similarities (cx0, cy0, s0, cx1, cy1, s1) of fp64 pixel arrays (n, 2)."""
+    n = P0.shape[0]
+    c = PR.block_sums(np.c_[P0, P1]) if n else np.zeros(4)
+    dn = float(max(n, 1))
+    cx0, cy0, cx1, cy1 = (float(v) / dn for v in c)
+    with np.errstate(all="ignore"):
+        ax, ay, bx, by = P0[:, 0] - cx0, P0[:, 1] - cy0, P1[:, 0] - cx1, P1[:, 1] - cy1
+        d = PR.block_sums(np.c_[np.sqrt(ax * ax + ay * ay), np.sqrt(bx * bx + by * by)]) if n else np.zeros(2)
+        s0 = SQRT2 / (float(d[0]) / dn) if d[0] > 0.0 else 1.0
+        s1 = SQRT2 / (float(d[1]) / dn) if d[1] > 0.0 else 1.0
+    return (cx0, cy0, s0, cx1, cy1, s1)
+
+
+def normalised(P0, P1, nt):
+    cx0, cy0, s0, cx1, cy1, s1 = nt
+    return (P0[..., 0] - cx0) * s0, (P0[..., 1] - cy0) * s0, (P1[..., 0] - cx1) * s1, (P1[..., 1] - cy1) * s1
+
+
+def iterations_needed(inliers, n, log1mc, max_iters):
+    w = inliers / n
+    p = 1.0 - ((((((w * w) * w) * w) * w) * w) * w)
+    if p <= 0.0:
+        return 1
+    if p >= 1.0:
+        return max_iters
+    k = math.ceil(log1mc / math.log(p))
+    return k if k < max_iters else max_iters
+
+
+def quality(r2, thr2, tmax2, bin_scale, stab):
+    """(integer MAGSAC++ quality, inlier count) per row of r2 (..., n)."""
+    with np.errstate(invalid="ignore"):
+        near = r2 < tmax2
+        b = np.minimum(np.where(near, r2 * bin_scale, 0.0).astype(np.int64), NBINS - 1)
+        q = np.where(near, stab[b].astype(np.int64), 0).sum(axis=-1)
+        cnt = (r2 < thr2).sum(axis=-1)
+    return q, cnt
+
+
+def hypotheses(P0, P1, nt, seed, pair, its, thr, tab):
+    """Qualities (H, 3) int64 (-1 where no candidate), inlier counts (H, 3), candidates (H, 3, 9), ncand (H,)."""
+    n = P0.shape[0]
+    bin_scale, stab, _ = tab
+    idx, ok = draws(seed, pair, its, n)
+    ii = np.where(ok[:, None], idx, 0)
+    X = normalised(P0[ii], P1[ii], nt)
+    cand, nc = solve(*X, nt)
+    nc = np.where(ok, nc, 0)
+    H = len(its)
+    qs = np.full((H, MAX_CAND), -1, np.int64)
+    cnts = np.zeros((H, MAX_CAND), np.int64)
+    thr2, tmax2 = thr * thr, (MAX_THR_FACTOR * thr) ** 2
+    with np.errstate(all="ignore"):
+        for c in range(MAX_CAND):
+            sel = np.nonzero(nc > c)[0]
+            if not len(sel):
+                continue
+            F = [cand[sel, c, k][:, None] for k in range(9)]
+            r2 = sampson(F, P0[None, :, 0], P0[None, :, 1], P1[None, :, 0], P1[None, :, 1])
+            qs[sel, c], cnts[sel, c] = quality(r2, thr2, tmax2, bin_scale, stab)
+    return qs, cnts, cand, nc
+
+
+def refine_terms(P0, P1, F, nt, thr, tab, robust=True):
+    """Quality (int) and the 45 per-correspondence terms of one refinement pass (FM_8POINT: unit weights, every point)."""
+    bin_scale, stab, wtab = tab if robust else (1.0, None, None)
+    tmax2 = (MAX_THR_FACTOR * thr) ** 2
+    x0, y0, x1, y1 = normalised(P0, P1, nt)
+    with np.errstate(all="ignore"):
+        if robust:
+            r2 = sampson(F, P0[:, 0], P0[:, 1], P1[:, 0], P1[:, 1])
+            near = r2 < tmax2
+            b = np.minimum(np.where(near, r2 * bin_scale, 0.0).astype(np.int64), NBINS - 1)
+            q = int(np.where(near, stab[b].astype(np.int64), 0).sum())
+            w = wtab[b]
+        else:
+            near = np.ones(P0.shape[0], bool)
+            q, w = 0, np.ones(P0.shape[0])
+        r = [x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, np.ones_like(x0)]
+        T = np.zeros((P0.shape[0], 45))
+        k = 0
+        for i in range(9):
+            wi = w * r[i]
+            for j in range(i, 9):
+                T[:, k] = np.where(near, wi * r[j], 0.0)
+                k += 1
+    return q, T
+
+
+def _info_word(v):
+    v &= 0xffffffff
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def estimate(pts0, pts1, ransac_thr=3.0, max_iters=1000, confidence=0.99, seed=0, pair=0, method=USAC_MAGSAC, tab=None):
+    """One pair.  Returns dict F (3, 9) (the output rows), mask (n,) uint8, info (8,) int -- the kernels' outputs for this pair (`pair` = its
+    index in the batch, which enters the draws).  tab: (bin_scale, quality table, weight table); default: tables(ransac_thr)."""
+    P0 = np.asarray(pts0, np.float32).astype(np.float64).reshape(-1, 2)
+    P1 = np.asarray(pts1, np.float32).astype(np.float64).reshape(-1, 2)
+    n = P0.shape[0]
+    thr = float(ransac_thr)
+    out_F = np.zeros((MAX_CAND, 9))
+    zero_mask = np.zeros(n, np.uint8)
+    nt = conditioning(P0, P1)
+    if method == FM_7POINT:
+        if n != 7:
+            return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
+        cand, nc = solve(*normalised(P0[None], P1[None], nt), nt, oriented=False)
+        nc = int(nc[0])
+        for c in range(nc):
+            out_F[c] = scale_out(cand[0, c])
+        return dict(F=out_F, mask=np.full(n, 1 if nc else 0, np.uint8), info=np.array([int(nc > 0), -1, nc, 7 if nc else 0, 0, n, 0, 0]))
+    if method == FM_8POINT:
+        if n < 8:
+            return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
+        _, T = refine_terms(P0, P1, None, nt, thr, None, robust=False)
+        Fp = fit8(PR.block_sums(T), nt)
+        if Fp is None:
+            return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
+        out_F[0] = scale_out(Fp)
+        return dict(F=out_F, mask=np.ones(n, np.uint8), info=np.array([1, -1, 1, n, 0, n, 0, 0]))
+    if method != USAC_MAGSAC:
+        raise ValueError(f"method {method}")
+    tab = tables(thr) if tab is None else tab
+    log1mc = math.log(1.0 - confidence)
+    if n < 7:
+        return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
+    best, best_q, best_F, stop, it, h = -1, 0, None, max_iters, 0, 0
+    done = False
+    for base in range(0, max_iters, 256):
+        its = np.arange(base, min(base + 256, max_iters))
+        qs, cnts, cand, nc = hypotheses(P0, P1, nt, seed, pair, its, thr, tab)
+        for i, h in enumerate(its):
+            if h >= stop:
+                done = True
+                break
+            if nc[i] > 0:
+                c = int(np.argmax(qs[i, :nc[i]]))            # first maximum
+                if qs[i, c] > best_q:
+                    best, best_q, best_F = int(h), int(qs[i, c]), cand[i, c].copy()
+                    stop = min(stop, iterations_needed(int(cnts[i, c]), n, log1mc, max_iters))
+            it = int(h) + 1
+        if done:
+            it = int(h)
+            break
+    if best < 0:
+        return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, it, 0, 0, n, 0, 0]))
+    Fc = [float(v) for v in best_F]
+    Fb, s_best, lo = Fc, 0, 0
+    for step in range(LO_ITERS + 1):
+        s_now, T = refine_terms(P0, P1, Fc, nt, thr, tab)
+        if s_now <= s_best:
+            break
+        Fb, s_best, lo = Fc, s_now, step
+        if step == LO_ITERS:
+            break
+        up = fit8(PR.block_sums(T), nt)
+        if up is None:
+            break
+        Fc = up
+    with np.errstate(all="ignore"):
+        m = sampson(Fb, P0[:, 0], P0[:, 1], P1[:, 0], P1[:, 1]) < thr * thr
+    n_in = int(m.sum())
+    found = n_in >= 7
+    info = np.array([int(found), best, it, n_in if found else 0, lo, n, _info_word(s_best), _info_word(s_best >> 32)])
+    if found:
+        out_F[0] = scale_out(Fb)
+    return dict(F=out_F, mask=(m & found).astype(np.uint8), info=info)
+
+
+# ---- ground truth and test data ---------------------------------------------------------------------------------------------------------
+def true_F(K0, K1, T_0to1):
+    """F = K1^-T [t]x R K0^-1 of X1 = R X0 + t (unit Frobenius norm)."""
+    T = np.asarray(T_0to1, np.float64)
+    F = np.linalg.inv(np.asarray(K1, np.float64)).T @ PR.essential_from_pose(T[:3, :3], T[:3, 3]) @ np.linalg.inv(np.asarray(K0, np.float64))
+    return F / np.linalg.norm(F)
+
+
+def f_distance(F, G):
+    """Distance of two F up to scale and sign: min over the sign of |F/|F| -+ G/|G||_F."""
+    F = np.asarray(F, np.float64).reshape(3, 3)
+    G = np.asarray(G, np.float64).reshape(3, 3)
+    F, G = F / np.linalg.norm(F), G / np.linalg.norm(G)
+    return min(np.linalg.norm(F - G), np.linalg.norm(F + G))
+
+
+def sampson_px(F, p0, p1):
+    """Sampson errors (pixels, not squared) of correspondences p0, p1 (n, 2) under F (3, 3)."""
+    F = np.asarray(F, np.float64).reshape(-1)
+    p0, p1 = np.asarray(p0, np.float64), np.asarray(p1, np.float64)
+    return np.sqrt(sampson(F, p0[:, 0], p0[:, 1], p1[:, 0], p1[:, 1]))
+
+
+# median Sampson error (px) of 200 held-out noise-free true correspondences per pair under the estimated F, over the synthetic
+# MegaDepth-1500 set at 1000 iterations, thr 1.5 px, seed 0.  The restatement finds F on every 25th pair (all 60) with a median over
+# pairs of 0.048 px and a 90th percentile of 0.084 px (test_fundamental_reference.py::test_megadepth_synthetic_holdout_error_on_every_25th_pair
+# computes them); the floors leave a margin for the pairs it does not run.  test_gpu_fundamental.py holds the kernels over all 1500 pairs to them.
+HOLDOUT_FLOORS = {"median": 0.15, "p90": 0.5, "found": 0.98}

@@ -1,0 +1,162 @@
+"""fm_solve and fm_fit8 (csrc/k_fundamental.hip) compiled for the HOST (tests/emu/fundamental_emu.cpp, fp contraction off) against the numpy
+restatement tests/fundamental_reference.py: on random, noise-free, noisy and near-degenerate samples the candidates must be equal bit for
+bit, and so must the 8-point fit; a negative control edits the slice and shows the comparison notices."""
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import fundamental_reference as FR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "accelerated_features_amd", "csrc")
+EMU = os.path.join(ROOT, "tests", "emu")
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+
+
+def _slice():
+    t = open(os.path.join(CSRC, "k_fundamental.hip")).read()
+    a = t.index("// ---- fm solver begin")
+    s = t[a:t.index("// ---- fm solver end", a)]
+    assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
+    return s.replace("__device__ ", "")
+
+
+def _build(src):
+    if not os.path.exists(CLANG):
+        pytest.skip("no host clang")
+    td = tempfile.mkdtemp()
+    open(os.path.join(td, "fundamental_slice.hpp"), "w").write(src)
+    out = os.path.join(td, "fundamental_emu")
+    subprocess.run([CLANG, "-O2", "-w", "-std=c++20", "-ffp-contract=off", "-I", td, "-I", EMU, os.path.join(EMU, "fundamental_emu.cpp"), "-o",
+                    out], check=True)
+    return out
+
+
+@pytest.fixture(scope="module")
+def emu_bin():
+    return _build(_slice())
+
+
+def _run_solve(emu_bin, X, nt, oriented=True):
+    H = X[0].shape[0]
+    blob = np.int32(0).tobytes() + np.int32(H).tobytes() + np.int32(int(oriented)).tobytes()
+    blob += b"".join(np.ascontiguousarray(v, np.float64).tobytes() for v in X) + np.ascontiguousarray(nt, np.float64).tobytes()
+    out = subprocess.run([emu_bin], input=blob, capture_output=True, check=True, timeout=600).stdout
+    return np.frombuffer(out[4 * H:], np.float64).reshape(H, 3, 9), np.frombuffer(out[:4 * H], np.int32)
+
+
+def _run_fit(emu_bin, sums, nt):
+    H = sums.shape[0]
+    blob = np.int32(1).tobytes() + np.int32(H).tobytes() + np.ascontiguousarray(sums, np.float64).tobytes()
+    blob += np.ascontiguousarray(nt, np.float64).tobytes()
+    out = subprocess.run([emu_bin], input=blob, capture_output=True, check=True, timeout=600).stdout
+    return np.frombuffer(out[:4 * H], np.int32), np.frombuffer(out[4 * H:], np.float64).reshape(H, 9)
+
+
+def _rotation(rng, scale):
+    w = rng.normal(size=3) * scale
+    th = np.linalg.norm(w)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+
+
+def _samples(rng, H):
+    """7-point samples in normalised coordinates, four kinds: uniform noise, noise-free scenes, noisy scenes, near-degenerate (coplanar,
+    collinear in one image, a repeated point); and a random conditioning per sample."""
+    x = rng.uniform(-1.5, 1.5, (4, H, 7))
+    kind = np.arange(H) % 4
+    for h in np.nonzero(kind > 0)[0]:
+        R, t = _rotation(rng, 0.3), rng.normal(size=3)
+        X = np.c_[rng.uniform(-1, 1, (7, 2)), rng.uniform(2, 6, 7)]
+        if kind[h] == 3:
+            sub = h % 3
+            if sub == 0:
+                X[:, 2] = 4.0 + 0.1 * X[:, 0]                   # coplanar
+            elif sub == 1:
+                X[:, 1] = 0.3 * X[:, 2]                         # all on one plane through the first centre: collinear in image 0
+            else:
+                X[6] = X[5] * (1 + 1e-9)                         # a repeated point
+        X2 = X @ R.T + t
+        x[0, h], x[1, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2]
+        x[2, h], x[3, h] = X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
+        if kind[h] == 2:
+            x[:, h] += rng.normal(size=(4, 7)) * 1e-3
+    nt = np.c_[rng.uniform(100, 900, (H, 2)), rng.uniform(1e-3, 1e-2, H), rng.uniform(100, 900, (H, 2)), rng.uniform(1e-3, 1e-2, H)]
+    return x, nt
+
+
+def _compare(cand, nc, want, wnc):
+    assert np.array_equal(nc, wnc), np.nonzero(nc != wnc)[0][:10]
+    for h in range(len(nc)):
+        if not np.array_equal(cand[h, :nc[h]].view(np.uint64), want[h, :nc[h]].view(np.uint64)):
+            return h
+    return None
+
+
+@pytest.mark.parametrize("oriented", [True, False])
+def test_host_solver_equals_the_restatement_bit_for_bit(emu_bin, oriented):
+    rng = np.random.default_rng(2025 + oriented)
+    H = 12000
+    x, nt = _samples(rng, H)
+    cand, nc = _run_solve(emu_bin, x, nt, oriented)
+    want, wnc = FR.solve(*x, nt.T, oriented=oriented)
+    assert _compare(cand, nc, want, wnc) is None
+    assert (nc > 0).mean() > 0.5
+    assert np.isfinite(cand).all()
+
+
+def test_host_solver_on_degenerate_and_non_finite_samples(emu_bin):
+    H = 4
+    x = np.zeros((4, H, 7))
+    x[:, 1] = 0.3                                      # all seven points identical
+    x[:, 2] = np.random.default_rng(0).uniform(-1, 1, (4, 7))
+    x[0, 2, 3] = np.nan                                 # a NaN coordinate
+    x[:, 3] = np.random.default_rng(1).uniform(-1, 1, (4, 7))
+    x[2, 3], x[3, 3] = x[0, 3], x[1, 3]                # identity motion: x1 = x0
+    nt = np.tile([0.0, 0.0, 1.0, 0.0, 0.0, 1.0], (H, 1))
+    cand, nc = _run_solve(emu_bin, x, nt)
+    want, wnc = FR.solve(*x, nt.T)
+    assert list(nc) == list(wnc)
+    assert nc[0] == 0 and nc[1] == 0 and nc[2] == 0
+    assert np.isfinite(cand).all()
+
+
+def test_host_fit8_equals_the_restatement_bit_for_bit(emu_bin):
+    rng = np.random.default_rng(7)
+    H = 300
+    sums, nts = np.zeros((H, 45)), np.zeros((H, 6))
+    for h in range(H):
+        R, t = _rotation(rng, 0.4), rng.normal(size=3)
+        n = int(rng.integers(8, 200))
+        X = np.c_[rng.uniform(-1, 1, (n, 2)), rng.uniform(2, 6, n)]
+        X2 = X @ R.T + t
+        x0, y0 = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2]
+        x1, y1 = X2[:, 0] / X2[:, 2] + rng.normal(size=n) * 1e-3 * (h % 2), X2[:, 1] / X2[:, 2]
+        w = rng.uniform(0, 1, n) if h % 3 else np.ones(n)
+        r = [x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, np.ones(n)]
+        T = np.stack([(w * r[i]) * r[j] for i in range(9) for j in range(i, 9)], axis=1)
+        sums[h] = FR.PR.block_sums(T)
+        nts[h] = [rng.uniform(0, 900), rng.uniform(0, 900), rng.uniform(1e-3, 1e-2), rng.uniform(0, 900), rng.uniform(0, 900), rng.uniform(1e-3, 1e-2)]
+    ok, F = _run_fit(emu_bin, sums, nts)
+    for h in range(H):
+        want = FR.fit8(sums[h], nts[h])
+        assert ok[h] == (want is not None)
+        if want is not None:
+            assert np.array_equal(F[h].view(np.uint64), np.array(want).view(np.uint64)), h
+
+
+def test_negative_control_an_edited_solver_is_caught():
+    """One re-associated sum in the slice (the denormalisation's translation column) must break the bit-for-bit comparison."""
+    src = _slice()
+    edited = src.replace("Fn[3 * i + 2] - (Fn[3 * i] * tx0 + Fn[3 * i + 1] * ty0)", "(Fn[3 * i + 2] - Fn[3 * i] * tx0) - Fn[3 * i + 1] * ty0")
+    assert edited != src
+    emu = _build(edited)
+    rng = np.random.default_rng(11)
+    x, nt = _samples(rng, 400)
+    cand, nc = _run_solve(emu, x, nt)
+    want, wnc = FR.solve(*x, nt.T)
+    assert not np.array_equal(nc, wnc) or _compare(cand, nc, want, wnc) is not None
