@@ -7,12 +7,11 @@
 // restates it in numpy operation for operation, tests/test_fundamental_emulated.py compiles the solver below on the host and holds it
 // to that restatement bit for bit):
 //   * conditioning: per pair a Hartley similarity, centroid c then scale s = sqrt(2) / (mean distance to c), both from fixed-order block
-//     sums (fundamental_prep_kernel); x_n = (x - c) s.  The solver works in normalised coordinates, the score in pixels;
-//   * sample: 7 distinct correspondences; draw d of hypothesis `it` of pair p is the upper half of
-//     splitmix64-finaliser(seed + golden * (((p << 20) + it) * 16 + d + 1)) scaled to [0, n) (the construction of k_homography.hip);
-//     duplicates are redrawn, 16 draws at most; a sample that runs out of draws yields no model;
+//     sums (fundamental_prep_kernel, rs::hartley_conditioning of ransac_common.hpp); x_n = (x - c) s.  The solver works in normalised coordinates, the score in pixels;
+//   * sample: 7 distinct correspondences, drawn as ransac_common.hpp states (splitmix64 of (seed, pair, hypothesis, draw); duplicates
+//     are redrawn, 16 draws at most; a sample that runs out of draws yields no model);
 //   * minimal solver (fm_solve): null space (F1, F2) of the 7x9 constraint matrix by Gauss-Jordan with partial pivoting (a pivot below
-//     FM_PIVOT_EPS or not finite: no model); det(F2 + a (F1 - F2)) = c3 a^3 + c2 a^2 + c1 a + c0 by polynomial products in a fixed order,
+//     tv::PIVOT_EPS of twoview_math.hpp or not finite: no model); det(F2 + a (F1 - F2)) = c3 a^3 + c2 a^2 + c1 a + c0 by polynomial products in a fixed order,
 //     made monic (c3 zero or not finite: no model); its real roots with + - * / sqrt only: the derivative's roots split [-B, B]
 //     (B = 1 + max |a_k|, Cauchy) into monotone brackets, each bracket with a sign change gets BISECT_STEPS bisections on the sign, then
 //     NEWTON_STEPS Newton steps, each kept only if it lowers |p|; roots in ascending order, at most 3;
@@ -22,9 +21,10 @@
 //     + (F' x1)_2^2); MAGSAC++ quality = sum over r^2 < (2 thr)^2 of the 20-bit table entry of r^2's bin (the homography's tables:
 //     n = 4 degrees of freedom, k = 3.64, sigma_max = 2 thr / k, 4096 bins), summed as u64 (no summation order); inlier: r^2 < thr^2
 //     (NaN: never); a hypothesis scores the best of its candidates (ties: the lower root);
-//   * stopping rule: hypotheses in order, a strictly better quality bounds the loop by ceil(log(1 - confidence) / log(1 - w^7));
+//   * stopping rule: hypotheses in order, a strictly better quality bounds the loop by ceil(log(1 - confidence) / log(1 - w^7))
+//     (rs::scan_stopping_rule of ransac_common.hpp);
 //   * refinement of the winner: up to LO_ITERS re-weighted 8-point fits (Hartley-normalised, weights w(r) / w(0) from the same bins),
-//     the 45 sums of the 9x9 normal matrix from fixed-order block reductions, its smallest eigenvector by cyclic Jacobi (JACOBI_SWEEPS
+//     the 45 sums of the 9x9 normal matrix from fixed-order block reductions (rs::block_sums), its smallest eigenvector by cyclic Jacobi (JACOBI_SWEEPS
 //     sweeps), rank 2 by removing the smallest singular value (smallest eigenvector v of Fn' Fn, Fn <- Fn - (Fn v) v'), each step kept
 //     only if it raises the quality;
 //   * mask: r^2 < thr^2 under the final F; found = at least 7 inliers; F scaled to unit Frobenius norm, then divided by F[2,2] when
@@ -46,91 +46,33 @@
 //   fundamental_score_kernel    : thread = hypothesis, its candidates in turn against a chunk of correspondences in LDS, u64 atomics
 //   fundamental_bound_kernel    : the bound the loop reaches from the records among the first 256; later blocks run only below it
 //   fundamental_select_kernel   : one workgroup per pair: stopping rule over the score list (tiles in LDS), refinement, mask, outputs
-#include "kernels.hpp"
+#include "ransac_common.hpp"
+#include "twoview_math.hpp"
 
 #pragma clang fp contract(off)
 
 namespace xfh {
 namespace fm {
-constexpr int MAX_DRAWS = 16, LO_ITERS = 5, MAX_ITERS = 16384, NBINS = 4096;
-constexpr int SOLVE_WG = 64, HYP_PER_WG = 256, PTS_PER_WG = 512, SEL_TILE = 2048, SEL_CACHE = 2048, NSUM = 45;
+using rs::NBINS, rs::HYP_PER_WG, rs::PTS_PER_WG, rs::SEL_TILE, rs::SEL_CACHE;
+constexpr int LO_ITERS = 5, MAX_ITERS = 16384, SOLVE_WG = 64, NSUM = 45;
 constexpr double MAX_THR_FACTOR = 2.0;          // the tables (k = 3.64, 4096 bins) are the homography's
 constexpr int METHOD_7POINT = 1, METHOD_8POINT = 2, METHOD_MAGSAC = 38;
 }  // namespace fm
 
-// ---- fm solver begin (host-compilable: tests/test_fundamental_emulated.py slices it out and drops the __device__ qualifiers) ----
+// ---- fm solver begin (host-compilable: tests/test_fundamental_emulated.py slices it out behind the slice of twoview_math.hpp and drops
+// the __device__ qualifiers) ----
 namespace fm {
 constexpr int MAX_CAND = 3, SLICE = 91, BISECT_STEPS = 64, NEWTON_STEPS = 3, JACOBI_SWEEPS = 10;
 constexpr double FLT_EPS = 1.1920928955078125e-07, FIT_RANK_EPS = 1e-12;
 }  // namespace fm
-constexpr double FM_PIVOT_EPS = 1e-12;
 // slice layout (fp64 elements): [0, 63) the 7x9 constraint matrix, [63, 91) the sample: x0[7] y0[7] x1[7] y1[7] (normalised)
 constexpr int FM_M = 0, FM_PTS = 63;
-
-template <int ST>
-struct FmSlice {
-    double* b;
-    __device__ inline double& operator[](int k) const { return b[k * ST]; }
-};
 
 // the pair's Hartley similarities: x_n = (x - cx) s
 struct FmNorm {
     double cx0, cy0, s0, cx1, cy1, s1;
 };
 
-__device__ inline bool fm_finite(double v) { return v - v == 0.0; }
-__device__ inline void fm_cross(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ inline double fm_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// Sampson error of x0 = (a, b, 1), x1 = (c, d, 1) under F (x1' F x0 = 0)
-__device__ inline double fm_sampson(const double* F, double a, double b, double c, double d) {
-    const double e0 = (F[0] * a + F[1] * b) + F[2], e1 = (F[3] * a + F[4] * b) + F[5], e2 = (F[6] * a + F[7] * b) + F[8];
-    const double f0 = (F[0] * c + F[3] * d) + F[6], f1 = (F[1] * c + F[4] * d) + F[7];
-    const double num = (c * e0 + d * e1) + e2;
-    const double den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1;
-    return num * num / den;
-}
-
-// Gauss-Jordan with partial pivoting on the first `rows` columns of a rows x cols matrix at S[base + r * cols + c]; false if degenerate
-template <class S>
-__device__ inline bool fm_gauss_jordan(S s, int base, int rows, int cols) {
-    for (int c = 0; c < rows; ++c) {
-        int p = c;
-        double best = fabs(s[base + c * cols + c]);
-        for (int r = c + 1; r < rows; ++r) {
-            const double v = fabs(s[base + r * cols + c]);
-            if (v > best) { best = v; p = r; }
-        }
-        if (!(best >= FM_PIVOT_EPS)) return false;
-        if (p != c)
-            for (int j = c; j < cols; ++j) {
-                const double tmp = s[base + c * cols + j];
-                s[base + c * cols + j] = s[base + p * cols + j];
-                s[base + p * cols + j] = tmp;
-            }
-        const double inv = 1.0 / s[base + c * cols + c];
-        for (int j = c + 1; j < cols; ++j) s[base + c * cols + j] = s[base + c * cols + j] * inv;
-        s[base + c * cols + c] = 1.0;
-        for (int r = 0; r < rows; ++r) {
-            if (r == c) continue;
-            const double f = s[base + r * cols + c];
-            for (int j = c + 1; j < cols; ++j) s[base + r * cols + j] = s[base + r * cols + j] - f * s[base + c * cols + j];
-            s[base + r * cols + c] = 0.0;
-        }
-    }
-    return true;
-}
-
-// poly product c[0..da+db] = a * b (ascending powers), accumulated in the order i, j
-__device__ inline void fm_pmul(const double* a, int da, const double* b, int db, double* c) {
-    for (int k = 0; k <= da + db; ++k) c[k] = 0.0;
-    for (int i = 0; i <= da; ++i)
-        for (int j = 0; j <= db; ++j) c[i + j] = c[i + j] + a[i] * b[j];
-}
 // monic cubic x^3 + a2 x^2 + a1 x + a0 and its derivative (b2 = 2 a2)
 __device__ inline double fm_cubic(const double* a, double x) { return ((x + a[2]) * x + a[1]) * x + a[0]; }
 __device__ inline double fm_dcubic(const double* a, double b2, double x) { return (3.0 * x + b2) * x + a[1]; }
@@ -141,7 +83,7 @@ __device__ inline int fm_cubic_roots(const double* a, double* roots) {
     bound = fabs(a[1]) > bound ? fabs(a[1]) : bound;
     bound = fabs(a[2]) > bound ? fabs(a[2]) : bound;
     bound = 1.0 + bound;
-    if (!fm_finite(bound)) return 0;
+    if (!tv::is_finite(bound)) return 0;
     // brackets [e0, e1], [e1, e2], [e2, e3]: split at the derivative's roots when it has two, else one bracket [-B, B]
     double e[4] = {-bound, bound, bound, bound};
     const double disc = a[2] * a[2] - 3.0 * a[1];
@@ -203,7 +145,7 @@ __device__ inline int fm_solve(S s, const FmNorm& nt, bool oriented, double* out
 #pragma unroll
         for (int j = 0; j < 9; ++j) s[FM_M + 9 * k + j] = r[j];
     }
-    if (!fm_gauss_jordan(s, FM_M, 7, 9)) return 0;
+    if (!tv::gauss_jordan(s, FM_M, 7, 9)) return 0;
     // null vectors (-C[:, k], e_k) of the reduced matrix [I | C]; F(a) = F2 + a D, D = F1 - F2
     double f2[9], D[9];
 #pragma unroll
@@ -220,25 +162,25 @@ __device__ inline int fm_solve(S s, const FmNorm& nt, bool oriented, double* out
 #pragma unroll
         for (int i = 0; i < 9; ++i) { m[i][0] = f2[i]; m[i][1] = D[i]; }
         double t1[3], t2[3], q0[3], q1[3], q2[3], w[4];
-        fm_pmul(m[4], 1, m[8], 1, t1); fm_pmul(m[5], 1, m[7], 1, t2);
+        tv::pmul(m[4], 1, m[8], 1, t1); tv::pmul(m[5], 1, m[7], 1, t2);
 #pragma unroll
         for (int k = 0; k < 3; ++k) q0[k] = t1[k] - t2[k];
-        fm_pmul(m[3], 1, m[8], 1, t1); fm_pmul(m[5], 1, m[6], 1, t2);
+        tv::pmul(m[3], 1, m[8], 1, t1); tv::pmul(m[5], 1, m[6], 1, t2);
 #pragma unroll
         for (int k = 0; k < 3; ++k) q1[k] = t1[k] - t2[k];
-        fm_pmul(m[3], 1, m[7], 1, t1); fm_pmul(m[4], 1, m[6], 1, t2);
+        tv::pmul(m[3], 1, m[7], 1, t1); tv::pmul(m[4], 1, m[6], 1, t2);
 #pragma unroll
         for (int k = 0; k < 3; ++k) q2[k] = t1[k] - t2[k];
-        fm_pmul(m[0], 1, q0, 2, c);
-        fm_pmul(m[1], 1, q1, 2, w);
+        tv::pmul(m[0], 1, q0, 2, c);
+        tv::pmul(m[1], 1, q1, 2, w);
 #pragma unroll
         for (int k = 0; k < 4; ++k) c[k] = c[k] - w[k];
-        fm_pmul(m[2], 1, q2, 2, w);
+        tv::pmul(m[2], 1, q2, 2, w);
 #pragma unroll
         for (int k = 0; k < 4; ++k) c[k] = c[k] + w[k];
     }
     const double lead = c[3];
-    if (!(fabs(lead) > 0.0) || !fm_finite(lead)) return 0;
+    if (!(fabs(lead) > 0.0) || !tv::is_finite(lead)) return 0;
     const double a[3] = {c[0] / lead, c[1] / lead, c[2] / lead};
     double roots[3] = {0.0, 0.0, 0.0};
     const int nr = fm_cubic_roots(a, roots);
@@ -250,14 +192,14 @@ __device__ inline int fm_solve(S s, const FmNorm& nt, bool oriented, double* out
         double Fn[9];
         bool ok = true;
 #pragma unroll
-        for (int m = 0; m < 9; ++m) { Fn[m] = f2[m] + z * D[m]; ok = ok && fm_finite(Fn[m]); }
+        for (int m = 0; m < 9; ++m) { Fn[m] = f2[m] + z * D[m]; ok = ok && tv::is_finite(Fn[m]); }
         if (!ok) continue;
         if (oriented) {
             // epipole e' in image 1 (e'' F = 0): the cross product of two columns of F, the pair with the largest norm
             const double k0[3] = {Fn[0], Fn[3], Fn[6]}, k1[3] = {Fn[1], Fn[4], Fn[7]}, k2[3] = {Fn[2], Fn[5], Fn[8]};
             double c01[3], c02[3], c12[3];
-            fm_cross(k0, k1, c01); fm_cross(k0, k2, c02); fm_cross(k1, k2, c12);
-            const double n01 = fm_dot(c01, c01), n02 = fm_dot(c02, c02), n12 = fm_dot(c12, c12);
+            tv::cross3(k0, k1, c01); tv::cross3(k0, k2, c02); tv::cross3(k1, k2, c12);
+            const double n01 = tv::dot3(c01, c01), n02 = tv::dot3(c02, c02), n12 = tv::dot3(c12, c12);
             const int tp = n12 > (n02 > n01 ? n02 : n01) ? 2 : (n02 > n01 ? 1 : 0);
             const double ne = tp == 0 ? n01 : (tp == 1 ? n02 : n12);
             double ep[3];
@@ -271,8 +213,8 @@ __device__ inline int fm_solve(S s, const FmNorm& nt, bool oriented, double* out
                 const double x1[3] = {s[FM_PTS + 14 + i], s[FM_PTS + 21 + i], 1.0};
                 const double fx[3] = {(Fn[0] * xa + Fn[1] * xb) + Fn[2], (Fn[3] * xa + Fn[4] * xb) + Fn[5], (Fn[6] * xa + Fn[7] * xb) + Fn[8]};
                 double ex[3];
-                fm_cross(ep, x1, ex);
-                const double v = fm_dot(ex, fx);
+                tv::cross3(ep, x1, ex);
+                const double v = tv::dot3(ex, fx);
                 pos += v > 0.0 ? 1 : 0;
                 neg += v < 0.0 ? 1 : 0;
             }
@@ -281,7 +223,7 @@ __device__ inline int fm_solve(S s, const FmNorm& nt, bool oriented, double* out
         double Fp[9];
         fm_denormalise(Fn, nt, Fp);
 #pragma unroll
-        for (int m = 0; m < 9; ++m) ok = ok && fm_finite(Fp[m]);
+        for (int m = 0; m < 9; ++m) ok = ok && tv::is_finite(Fp[m]);
         if (!ok) continue;
         double* o = out + 9 * ncand;
 #pragma unroll
@@ -370,7 +312,7 @@ __device__ inline bool fm_fit8(const double* sm, S A, S V, const FmNorm& nt, dou
     fm_denormalise(Fn, nt, Fp);
     bool fin = true;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) fin = fin && fm_finite(Fp[i]);
+    for (int i = 0; i < 9; ++i) fin = fin && tv::is_finite(Fp[i]);
     return fin;
 }
 
@@ -411,23 +353,6 @@ struct FmArgs {
     int32_t* info;
 };
 
-struct FmPts {
-    const float* p0;
-    const float* p1;
-    const int64_t* i0;
-    const int64_t* i1;
-    __device__ FmPts(const FmArgs& a, int pair)
-        : p0(a.p0 + (size_t)pair * a.kcap * 2), p1(a.p1 + (size_t)pair * a.kcap * 2), i0(a.idx0 ? a.idx0 + (size_t)pair * a.cap : nullptr),
-          i1(a.idx1 ? a.idx1 + (size_t)pair * a.cap : nullptr) {}
-    __device__ inline float4 get(int i) const {
-        const size_t r0 = i0 ? (size_t)i0[i] : (size_t)i, r1 = i1 ? (size_t)i1[i] : (size_t)i;
-        const float2 q0 = *reinterpret_cast<const float2*>(p0 + 2 * r0);
-        const float2 q1 = *reinterpret_cast<const float2*>(p1 + 2 * r1);
-        return make_float4(q0.x, q0.y, q1.x, q1.y);
-    }
-};
-
-__device__ inline int fm_count(const FmArgs& a, int pair) { return a.counts ? min(max(a.counts[pair], 0), a.cap) : a.n_const; }
 __device__ inline FmNorm fm_norm(const FmArgs& a, int pair) {
     const double* q = a.norm + (size_t)pair * 8;
     return FmNorm{q[0], q[1], q[2], q[3], q[4], q[5]};
@@ -435,85 +360,22 @@ __device__ inline FmNorm fm_norm(const FmArgs& a, int pair) {
 // minimum number of correspondences of the method
 __device__ inline int fm_min_n(const FmArgs& a) { return a.method == fm::METHOD_8POINT ? 8 : 7; }
 
-__device__ inline unsigned long long fm_mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ inline int fm_draw(unsigned long long seed, int pair, int it, int draw, int n) {
-    const unsigned long long counter = ((unsigned long long)pair * (1ull << 20) + (unsigned long long)it) * fm::MAX_DRAWS + (unsigned long long)draw;
-    const unsigned long long h = fm_mix64(seed + 0x9e3779b97f4a7c15ull * (counter + 1ull));
-    return (int)(((h >> 32) * (unsigned long long)n) >> 32);
-}
-__device__ inline int fm_bin(double r2, double bin_scale) {
-    const int b = (int)(r2 * bin_scale);
-    return b < fm::NBINS - 1 ? b : fm::NBINS - 1;
-}
-
-// Totals of N per-thread values over the 256 threads in a fixed order (thread i adds its own values in index order; then 8 segments of
-// 32 threads per value, each summed in order; then a tree over the 8) -- rp_block_sums of k_relpose.hip for any N
-constexpr int FM_RED_PITCH = 257;
-template <int N>
-__device__ inline void fm_block_sums(double (&v)[N], double* buf /* N * FM_RED_PITCH + 9 * N doubles */) {
-    const int tid = threadIdx.x;
-    double* part = buf + N * FM_RED_PITCH;
-    double* tot = part + N * 8;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) buf[k * FM_RED_PITCH + tid] = v[k];
-    __syncthreads();
-    for (int r = tid; r < N * 8; r += 256) {
-        const int k = r >> 3, j = r & 7;
-        const double* row = buf + k * FM_RED_PITCH + j * 32;
-        double t = 0.0;
-        for (int i = 0; i < 32; ++i) t += row[i];
-        part[r] = t;
-    }
-    __syncthreads();
-    for (int k = tid; k < N; k += 256) {
-        const double* q = part + k * 8;
-        tot[k] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = tot[k];
-}
-
 __global__ __launch_bounds__(256) void fundamental_zero_kernel(FmArgs a, size_t nhyp) {
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nhyp; j += (size_t)gridDim.x * 256) {
-        a.ncand[j] = 0;
-#pragma unroll
-        for (int c = 0; c < fm::MAX_CAND; ++c) { a.hscore[j * fm::MAX_CAND + c] = 0ull; a.hcnt[j * fm::MAX_CAND + c] = 0u; }
-    }
+    rs::zero_hypotheses<fm::MAX_CAND>(a.ncand, a.hscore, a.hcnt, nhyp);
 }
 
 // one workgroup per pair: the Hartley conditioning of both point sets
 __global__ __launch_bounds__(256) void fundamental_prep_kernel(FmArgs a) {
-    __shared__ double red[4 * FM_RED_PITCH + 36];
+    __shared__ double red[rs::block_sums_bytes(4) / sizeof(double)];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = fm_count(a, pair);
-    const FmPts pts(a, pair);
-    double c[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = tid; i < n; i += 256) {
-        const float4 q = pts.get(i);
-        c[0] += q.x; c[1] += q.y; c[2] += q.z; c[3] += q.w;
-    }
-    fm_block_sums(c, red);
-    const double dn = (double)(n > 0 ? n : 1);
-    const double cx0 = c[0] / dn, cy0 = c[1] / dn, cx1 = c[2] / dn, cy1 = c[3] / dn;
-    double dd[2] = {0.0, 0.0};
-    for (int i = tid; i < n; i += 256) {
-        const float4 q = pts.get(i);
-        const double ax = q.x - cx0, ay = q.y - cy0, bx = q.z - cx1, by = q.w - cy1;
-        dd[0] += sqrt(ax * ax + ay * ay);
-        dd[1] += sqrt(bx * bx + by * by);
-    }
-    fm_block_sums(dd, red);
+    const int n = rs::pair_count(a, pair);
+    const rs::PairView pts(a, pair);
+    double nt[6];
+    rs::hartley_conditioning([&](auto&& f) { for (int i = tid; i < n; i += 256) f(i, pts.get(i)); }, (double)(n > 0 ? n : 1), red, nt);
     if (tid == 0) {
         double* o = a.norm + (size_t)pair * 8;
-        o[0] = cx0; o[1] = cy0; o[2] = dd[0] > 0.0 ? 1.41421356237309504880 / (dd[0] / dn) : 1.0;
-        o[3] = cx1; o[4] = cy1; o[5] = dd[1] > 0.0 ? 1.41421356237309504880 / (dd[1] / dn) : 1.0;
-        o[6] = 0.0; o[7] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = k < 6 ? nt[k] : 0.0;
     }
 }
 
@@ -523,30 +385,15 @@ __global__ __launch_bounds__(64) void fundamental_solve_kernel(FmArgs a, int it_
     extern __shared__ __attribute__((aligned(16))) double fm_lds[];
     const int pair = blockIdx.y, tid = threadIdx.x;
     const int it = it_base + blockIdx.x * fm::SOLVE_WG + tid;
-    const int n = fm_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     const bool seven = a.method == fm::METHOD_7POINT;
     if (seven ? (n != 7 || it != 0) : (n < 7 || it >= a.iters)) return;
     if (use_bound && a.bound[pair] <= it) return;
-    const FmPts pts(a, pair);
-    int idx[7] = {0, 1, 2, 3, 4, 5, 6}, slot = 7;
-    if (!seven) {
-        slot = 0;
-#pragma unroll
-        for (int d = 0; d < fm::MAX_DRAWS; ++d) {
-            const int c = fm_draw(a.seed, pair, it, d, n);
-            bool dup = false;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) dup = dup || (slot > k && c == idx[k]);
-            if (slot < 7 && !dup) {
-#pragma unroll
-                for (int k = 0; k < 7; ++k) idx[k] = slot == k ? c : idx[k];
-                ++slot;
-            }
-        }
-    }
-    if (slot < 7) return;
+    const rs::PairView pts(a, pair);
+    int idx[7] = {0, 1, 2, 3, 4, 5, 6};
+    if (!seven && !rs::sample_distinct(a.seed, pair, it, n, idx)) return;
     const FmNorm nt = fm_norm(a, pair);
-    FmSlice<fm::SOLVE_WG> s{fm_lds + tid};
+    tv::Slice<fm::SOLVE_WG> s{fm_lds + tid};
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
         const float4 q = pts.get(idx[k]);
@@ -564,12 +411,12 @@ __global__ __launch_bounds__(256) void fundamental_score_kernel(FmArgs a, int bl
     __shared__ unsigned stab[fm::NBINS];
     __shared__ float4 spt[fm::PTS_PER_WG];
     const int pair = blockIdx.z, tid = threadIdx.x;
-    const int n = fm_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     const int c0 = blockIdx.y * a.chunk;
     const int it0 = (blockIdx.x + blk0) * fm::HYP_PER_WG;
     if (n < 7 || c0 >= n) return;
     if (use_bound && a.bound[pair] <= it0) return;
-    const FmPts pts(a, pair);
+    const rs::PairView pts(a, pair);
     const int c1 = min(c0 + a.chunk, n);
 #pragma unroll
     for (int k = 0; k < fm::NBINS / 256; ++k) stab[tid + 256 * k] = a.stab[tid + 256 * k];
@@ -590,9 +437,9 @@ __global__ __launch_bounds__(256) void fundamental_score_kernel(FmArgs a, int bl
 #pragma unroll 4
         for (int i = 0; i < m; ++i) {
             const float4 q = spt[i];
-            const double r2 = fm_sampson(F, q.x, q.y, q.z, q.w);
+            const double r2 = tv::sampson(F, q.x, q.y, q.z, q.w);
             const bool near = r2 < a.tmax2;
-            const unsigned e = stab[fm_bin(near ? r2 : 0.0, a.bin_scale)];
+            const unsigned e = stab[rs::bin_of(near ? r2 : 0.0, a.bin_scale)];
             sc += near ? e : 0u;
             cnt += r2 < a.thr2 ? 1u : 0u;
         }
@@ -601,47 +448,16 @@ __global__ __launch_bounds__(256) void fundamental_score_kernel(FmArgs a, int bl
     }
 }
 
-// iterations the loop still needs once a model with `inliers` of n is the best one
-__device__ inline int fm_iterations_needed(unsigned inliers, int n, double log1mc, int max_iters) {
-    const double w = (double)inliers / (double)n;
-    const double p = 1.0 - ((((((w * w) * w) * w) * w) * w) * w);
-    if (p <= 0.0) return 1;
-    if (p >= 1.0) return max_iters;
-    const double k = ceil(log1mc / log(p));
-    return k < (double)max_iters ? (int)k : max_iters;
-}
-// hypothesis quality (maximum over its candidates, the lower root on ties) and that candidate's inlier count; false: no model
-__device__ inline bool fm_hyp_quality(const FmArgs& a, size_t h, unsigned long long& q, unsigned& cnt, int& cand) {
-    const int nc = a.ncand[h];
-    if (nc <= 0) return false;
-    q = a.hscore[h * fm::MAX_CAND];
-    cnt = a.hcnt[h * fm::MAX_CAND];
-    cand = 0;
-    for (int c = 1; c < nc; ++c) {
-        const unsigned long long v = a.hscore[h * fm::MAX_CAND + c];
-        if (v > q) { q = v; cnt = a.hcnt[h * fm::MAX_CAND + c]; cand = c; }
-    }
-    return true;
-}
-
-// After the first 256 hypotheses: min over the records (strict prefix maxima of the quality) among them of the bound; see
-// homog_bound_kernel for why the records of the first block bound the loop
+// After the first 256 hypotheses: rs::hypotheses_bound over the records (strict prefix maxima of the quality) among them; a hypothesis
+// scores the maximum over its candidates (rs::hyp_best)
 __global__ __launch_bounds__(256) void fundamental_bound_kernel(FmArgs a) {
-    __shared__ unsigned long long sc[256];
-    __shared__ int bmin;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = fm_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     unsigned long long q = 0;
     unsigned cnt = 0;
     int cand = 0;
-    const bool has = tid < a.iters && n >= 7 && fm_hyp_quality(a, (size_t)pair * a.iters_pad + tid, q, cnt, cand);
-    sc[tid] = has ? q : 0ull;
-    if (tid == 0) bmin = a.iters;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (int j = 0; j < tid; ++j) before = sc[j] > before ? sc[j] : before;
-    if (has && q > before) atomicMin(&bmin, fm_iterations_needed(cnt, n, a.log1mc, a.iters));
-    __syncthreads();
+    const bool has = tid < a.iters && n >= 7 && rs::hyp_best<fm::MAX_CAND, false>(a.ncand, a.hscore, a.hcnt, (size_t)pair * a.iters_pad + tid, q, cnt, cand);
+    const int bmin = rs::hypotheses_bound<7, false>(has, q, cnt, n, a.log1mc, a.iters);
     if (tid == 0) a.bound[pair] = bmin;
 }
 
@@ -649,13 +465,12 @@ __global__ __launch_bounds__(256) void fundamental_bound_kernel(FmArgs a) {
 __global__ __launch_bounds__(256) void fundamental_select_kernel(FmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ double jA[81], jV[81], fsh[9];
-    __shared__ int sel[4];
-    __shared__ unsigned long long sc_sh, best_sh;
+    __shared__ unsigned long long sc_sh;
     __shared__ unsigned cnt_sh;
-    __shared__ int stop_sh, done_sh, ok_sh;
+    __shared__ int ok_sh;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = fm_count(a, pair);
-    const FmPts pts(a, pair);
+    const int n = rs::pair_count(a, pair);
+    const rs::PairView pts(a, pair);
     unsigned char* mask = a.mask + (size_t)pair * a.cap;
     int32_t* info = a.info + pair * 8;
     double* Fout = a.F + (size_t)pair * fm::MAX_CAND * 9;
@@ -676,62 +491,27 @@ __global__ __launch_bounds__(256) void fundamental_select_kernel(FmArgs a) {
     }
 
     // ---- the stopping rule of the sequential loop, over tiles of the score list
-    int best = -1, iters_run = 0;
+    int best = -1, best_cand = -1, iters_run = 0;
     if (robust) {
-        unsigned long long* tq = reinterpret_cast<unsigned long long*>(lds_raw);
-        unsigned* tn = reinterpret_cast<unsigned*>(lds_raw + (size_t)fm::SEL_TILE * 8);
-        int* tk = reinterpret_cast<int*>(lds_raw + (size_t)fm::SEL_TILE * 12);
-        if (tid == 0) { sel[0] = -1; sel[1] = 0; sel[2] = -1; best_sh = 0ull; stop_sh = a.iters; done_sh = n < 7 ? 1 : 0; }
-        __syncthreads();
-        for (int base = 0; base < a.iters; base += fm::SEL_TILE) {
-            if (done_sh) break;
-            for (int i = tid; i < fm::SEL_TILE; i += 256) {
-                const int it = base + i;
-                unsigned long long q = 0;
-                unsigned k = 0;
-                int cd = -1;
-                if (it < a.iters && it < stop_sh && !fm_hyp_quality(a, (size_t)pair * a.iters_pad + it, q, k, cd)) cd = -1;
-                tq[i] = q; tn[i] = k; tk[i] = cd;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int it = base;
-                int stop = stop_sh;
-                for (; it < a.iters && it < base + fm::SEL_TILE; ++it) {
-                    if (it >= stop) { done_sh = 1; break; }
-                    const int i = it - base;
-                    if (tk[i] >= 0 && tq[i] > best_sh) {
-                        best_sh = tq[i]; sel[0] = it; sel[2] = tk[i];
-                        const int need = fm_iterations_needed(tn[i], n, a.log1mc, a.iters);
-                        stop = need < stop ? need : stop;
-                    }
-                }
-                sel[1] = it;
-                stop_sh = stop;
-                if (it >= a.iters) done_sh = 1;
-            }
-            __syncthreads();
-        }
-        __syncthreads();
-        best = sel[0];
-        iters_run = n < 7 ? 0 : sel[1];
-        if (best >= 0 && tid < 9) fsh[tid] = a.cand[(((size_t)pair * a.iters_pad + best) * fm::MAX_CAND + sel[2]) * 9 + tid];
+        rs::scan_stopping_rule<7, false>(lds_raw, n, a.iters, 0, a.log1mc,
+                                         [&](int it, unsigned long long& q, unsigned& k, int& cd) {
+                                             return rs::hyp_best<fm::MAX_CAND, false>(a.ncand, a.hscore, a.hcnt, (size_t)pair * a.iters_pad + it, q, k, cd);
+                                         },
+                                         best, best_cand, iters_run);
+        if (best >= 0 && tid < 9) fsh[tid] = a.cand[(((size_t)pair * a.iters_pad + best) * fm::MAX_CAND + best_cand) * 9 + tid];
         __syncthreads();
     }
     if (robust ? best < 0 : n < 8) {
-        for (int i = tid; i < a.cap; i += 256) mask[i] = 0;
+        rs::write_nothing_found(mask, a.cap, info, iters_run, n);
         if (tid < 27) Fout[tid] = 0.0;
-        if (tid < 8) info[tid] = tid == 2 ? iters_run : (tid == 1 ? -1 : (tid == 5 ? n : 0));
         return;
     }
     const FmNorm nt = fm_norm(a, pair);
     double* red = reinterpret_cast<double*>(lds_raw);         // the tiles are dead: reduction buffer from here on
-    float4* spt = reinterpret_cast<float4*>(lds_raw + (((size_t)fm::NSUM * FM_RED_PITCH + 9 * fm::NSUM) * 8 + 31 & ~(size_t)31));
+    float4* spt = reinterpret_cast<float4*>(lds_raw + (rs::block_sums_bytes(fm::NSUM) + 31 & ~(size_t)31));
     for (int i = tid; i < min(n, fm::SEL_CACHE); i += 256) spt[i] = pts.get(i);
     __syncthreads();
-    auto for_each = [&](auto&& f) {
-        for (int i = tid; i < n; i += 256) f(i, i < fm::SEL_CACHE ? spt[i] : pts.get(i));
-    };
+    auto for_each = [&](auto&& f) { rs::for_each_cached(spt, n, [&](int i) { return pts.get(i); }, f); };
     // the 45 weighted sums of a a' of one pass; weight w(r)/w(0) of the bin of r^2 under F (FM_8POINT: 1 for every point), quality into sc_sh
     auto pass = [&](const double* F, double (&sm)[fm::NSUM]) {
         for (int k = 0; k < fm::NSUM; ++k) sm[k] = 0.0;
@@ -739,9 +519,9 @@ __global__ __launch_bounds__(256) void fundamental_select_kernel(FmArgs a) {
         for_each([&](int, const float4& q) {
             double w = 1.0;
             if (robust) {
-                const double r2 = fm_sampson(F, q.x, q.y, q.z, q.w);
+                const double r2 = tv::sampson(F, q.x, q.y, q.z, q.w);
                 if (!(r2 < a.tmax2)) return;
-                const int b = fm_bin(r2, a.bin_scale);
+                const int b = rs::bin_of(r2, a.bin_scale);
                 sc += a.stab[b];
                 w = a.wtab[b];
             }
@@ -757,7 +537,7 @@ __global__ __launch_bounds__(256) void fundamental_select_kernel(FmArgs a) {
             }
         });
         atomicAdd(&sc_sh, sc);
-        fm_block_sums(sm, red);                               // (its barriers also publish sc_sh)
+        rs::block_sums(sm, red);                               // (its barriers also publish sc_sh)
     };
     // one fit from the sums on thread 0 (LDS Jacobi), result into fsh / ok_sh
     auto fit = [&](const double (&sm)[fm::NSUM]) {
@@ -808,21 +588,19 @@ __global__ __launch_bounds__(256) void fundamental_select_kernel(FmArgs a) {
     __syncthreads();
     unsigned cn = 0;
     if (robust) {
-        for_each([&](int, const float4& q) { cn += fm_sampson(Fb, q.x, q.y, q.z, q.w) < a.thr2 ? 1u : 0u; });
+        for_each([&](int, const float4& q) { cn += tv::sampson(Fb, q.x, q.y, q.z, q.w) < a.thr2 ? 1u : 0u; });
         atomicAdd(&cnt_sh, cn);
     }
     __syncthreads();
     const int n_in = robust ? (int)cnt_sh : (model ? n : 0);
     const bool found = robust ? n_in >= 7 : model;
-    for_each([&](int i, const float4& q) { mask[i] = found && (!robust || fm_sampson(Fb, q.x, q.y, q.z, q.w) < a.thr2) ? 1 : 0; });
+    for_each([&](int i, const float4& q) { mask[i] = found && (!robust || tv::sampson(Fb, q.x, q.y, q.z, q.w) < a.thr2) ? 1 : 0; });
     for (int i = n + tid; i < a.cap; i += 256) mask[i] = 0;
     if (tid == 0) {
         double o[9];
         fm_scale_out(Fb, o);
         for (int k = 0; k < 27; ++k) Fout[k] = found && k < 9 ? o[k] : 0.0;
-        info[0] = found ? 1 : 0; info[1] = robust ? best : -1; info[2] = robust ? iters_run : (found ? 1 : 0); info[3] = found ? n_in : 0;
-        info[4] = lo_accepted; info[5] = n;
-        info[6] = (int)(s_best & 0xffffffffull); info[7] = (int)(s_best >> 32);
+        rs::write_info(info, found, robust ? best : -1, robust ? iters_run : (found ? 1 : 0), found ? n_in : 0, lo_accepted, n, s_best);
     }
 }
 
@@ -859,7 +637,7 @@ int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx
     a.ncand = reinterpret_cast<int*>(w);
     a.F = F; a.mask = mask; a.info = info;
     static AttrMask attr_sel = 0;
-    const size_t red = (((size_t)fm::NSUM * FM_RED_PITCH + 9 * fm::NSUM) * 8 + 31) & ~(size_t)31;
+    const size_t red = (rs::block_sums_bytes(fm::NSUM) + 31) & ~(size_t)31;
     const size_t tiles = (size_t)fm::SEL_TILE * 16;
     const size_t sel_lds = (red > tiles ? red : tiles) + (size_t)fm::SEL_CACHE * sizeof(float4);
     set_max_dynamic_lds(reinterpret_cast<const void*>(fundamental_select_kernel), (int)sel_lds, attr_sel);
@@ -878,8 +656,7 @@ int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx
     launch_homography_tables(thr, stab, wtab, st);
     const size_t zg = (nhyp + 255) / 256;
     fundamental_zero_kernel<<<(unsigned)(zg > 2048 ? 2048 : zg), 256, 0, st>>>(a, nhyp);
-    a.chunk = fm::PTS_PER_WG;
-    while (a.chunk > 64 && (long)P * ceil_div(cap, a.chunk) < 256) a.chunk >>= 1;
+    a.chunk = rs::score_chunk(P, cap);
     const int nblk = ceil_div(max_iters, fm::HYP_PER_WG), nch = ceil_div(cap, a.chunk);
     const int first = max_iters < fm::HYP_PER_WG ? max_iters : fm::HYP_PER_WG;
     fundamental_solve_kernel<<<dim3(ceil_div(first, fm::SOLVE_WG), P), fm::SOLVE_WG, solve_lds, st>>>(a, 0, 0);

@@ -4,13 +4,14 @@
 // USAC_MAGSAC -- RANSAC with the MAGSAC++ quality and sigma-consensus++ weights (Barath, Noskova, Ivashechkin, Matas, CVPR 2020) -- with
 // the call's arguments (threshold, maxIters, confidence).  The specification (the test suite holds an independent numpy
 // restatement of it):
-//   * minimal sample: 4 distinct correspondences; draw d of hypothesis `it` of pair p is the upper half of
-//     splitmix64-finaliser(seed + golden * (((p << 20) + it) * 16 + d + 1)) scaled to [0, n); duplicates are redrawn (16 draws at most);
+//   * minimal sample: 4 distinct correspondences, drawn as ransac_common.hpp states (splitmix64 of (seed, pair, hypothesis, draw);
+//     duplicates are redrawn, 16 draws at most);
 //   * 4-point homography H = B adj(A), A / B the projective bases through the first three source / target points that send (1,1,1) to
 //     the fourth (3x3 adjugates, no pivoting); a sample is rejected unless its four point triples all keep or all flip their orientation;
 //   * residual = squared forward transfer error; quality = sum over residuals below (2 thr)^2 of 1 - rho(r) / rho(k sigma_max), rho the
 //     MAGSAC++ loss for n = 4 degrees of freedom, k = 3.64, sigma_max = 2 thr / k, from a 4096-bin table over r^2 in 20-bit fixed point;
-//   * termination: hypotheses in order, a strictly better quality updates the bound log(1 - confidence) / log(1 - w^4), w = inlier ratio at thr;
+//   * termination: hypotheses in order, a strictly better quality updates the bound log(1 - confidence) / log(1 - w^4), w = inlier ratio at thr
+//     (the stopping rule of ransac_common.hpp for samples of 4, applied here to the whole list at once);
 //   * refinement of the winner: up to 5 re-weighted least-squares steps (Hartley-normalised inhomogeneous DLT, weights w(r) / w(0) from the
 //     same bins), each kept only if it raises the quality; mask = residual < thr^2 under the final model; found = at least 4 inliers.
 //
@@ -27,17 +28,16 @@
 //                         bounds the index the loop can still reach and the later hypothesis blocks run only below that bound (at 50 %
 //                         inliers the loop needs 83 iterations: the 444 hypotheses beyond the first block are never built)
 //   homog_select_kernel : one workgroup per pair: stopping rule, refinement (23 weighted sums -> block Cholesky of the 8x8 normal equations), mask
-#include "kernels.hpp"
+#include "ransac_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace xfh {
 namespace hg {
-constexpr int NBINS = 4096, SCORE_ONE = 1 << 20, LO_ITERS = 5, MAX_DRAWS = 16;
-constexpr int HYP_PER_WG = 256, PTS_PER_WG = 512, MAX_ITERS = 4096;
+using rs::NBINS, rs::HYP_PER_WG, rs::PTS_PER_WG, rs::SEL_CACHE;
+constexpr int SCORE_ONE = 1 << 20, LO_ITERS = 5, MAX_ITERS = 4096;
 constexpr double K_QUANTILE = 3.64, MAX_THR_FACTOR = 2.0;
 constexpr int NSUM = 23;
-constexpr int SEL_CACHE = 2048;     // correspondences of a pair that homog_select_kernel keeps in LDS
 }  // namespace hg
 
 struct HgArgs {
@@ -86,33 +86,7 @@ __global__ __launch_bounds__(256) void homog_tables_kernel(double thr, unsigned*
     for (int j = i; j < nhyp; j += gridDim.x * 256) { hscore[j] = 0ull; hcnt[j] = 0u; }
 }
 
-// ---- correspondences of one pair ---------------------------------------------------------------------------------------------------------
-struct PairPts {
-    const float* p0;
-    const float* p1;
-    const int64_t* i0;
-    const int64_t* i1;
-    __device__ PairPts(const HgArgs& a, int pair)
-        : p0(a.p0 + (size_t)pair * a.kcap * 2), p1(a.p1 + (size_t)pair * a.kcap * 2), i0(a.idx0 ? a.idx0 + (size_t)pair * a.cap : nullptr),
-          i1(a.idx1 ? a.idx1 + (size_t)pair * a.cap : nullptr) {}
-    __device__ inline void get(int i, float2& q0, float2& q1) const {
-        const size_t r0 = i0 ? (size_t)i0[i] : (size_t)i, r1 = i1 ? (size_t)i1[i] : (size_t)i;
-        q0 = *reinterpret_cast<const float2*>(p0 + 2 * r0);
-        q1 = *reinterpret_cast<const float2*>(p1 + 2 * r1);
-    }
-};
-
 // ---- hypotheses -------------------------------------------------------------------------------------------------------------------------
-__device__ inline unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ inline int draw_index(unsigned long long seed, int pair, int it, int draw, int n) {
-    const unsigned long long counter = ((unsigned long long)pair * (1ull << 20) + (unsigned long long)it) * hg::MAX_DRAWS + (unsigned long long)draw;
-    const unsigned long long h = mix64(seed + 0x9e3779b97f4a7c15ull * (counter + 1ull));
-    return (int)(((h >> 32) * (unsigned long long)n) >> 32);
-}
 __device__ inline double orient(double ax, double ay, double bx, double by, double cx, double cy) {
     return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
 }
@@ -127,25 +101,14 @@ __device__ inline void basis(const double (&x)[4], const double (&y)[4], double 
     for (int j = 0; j < 3; ++j) { m[0][j] = lam[j] * x[j]; m[1][j] = lam[j] * y[j]; m[2][j] = lam[j]; }
 }
 // hypothesis `it` of pair `pair`: false when the draws ran out or the sample does not keep the orientation of its triples
-__device__ inline bool make_hypothesis(const PairPts& pts, int n, unsigned long long seed, int pair, int it, double (&h)[9]) {
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1, slot = 0;
-#pragma unroll
-    for (int d = 0; d < hg::MAX_DRAWS; ++d) {
-        const int c = draw_index(seed, pair, it, d, n);
-        const bool dup = (slot > 0 && c == i0) || (slot > 1 && c == i1) || (slot > 2 && c == i2);
-        if (slot < 4 && !dup) {
-            i0 = slot == 0 ? c : i0; i1 = slot == 1 ? c : i1; i2 = slot == 2 ? c : i2; i3 = slot == 3 ? c : i3;
-            ++slot;
-        }
-    }
-    if (slot < 4) return false;
-    const int idx[4] = {i0, i1, i2, i3};
+__device__ inline bool make_hypothesis(const rs::PairView& pts, int n, unsigned long long seed, int pair, int it, double (&h)[9]) {
+    int idx[4] = {-1, -1, -1, -1};
+    if (!rs::sample_distinct(seed, pair, it, n, idx)) return false;
     double x0[4], y0[4], x1[4], y1[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float2 a, b;
-        pts.get(idx[k], a, b);
-        x0[k] = a.x; y0[k] = a.y; x1[k] = b.x; y1[k] = b.y;
+        const float4 q = pts.get(idx[k]);
+        x0[k] = q.x; y0[k] = q.y; x1[k] = q.z; y1[k] = q.w;
     }
     double A[3][3], Bm[3][3], da[4], db[4];
     basis(x0, y0, A, da);
@@ -176,42 +139,25 @@ __device__ inline double residual_sq(const double (&h)[9], double x, double y, d
     const double dx = u1 - u * iw, dy = v1 - v * iw;
     return dx * dx + dy * dy;
 }
-__device__ inline int bin_of(double r2, double bin_scale) {
-    const int b = (int)(r2 * bin_scale);
-    return b < hg::NBINS - 1 ? b : hg::NBINS - 1;
-}
-
-// iterations the loop still needs once a model with `inliers` of n is the best one (the standard RANSAC bound)
-__device__ inline int iterations_needed(unsigned inliers, int n, double log1mc, int max_iters) {
-    const double w = (double)inliers / (double)n;
-    const double p = 1.0 - w * w * w * w;
-    if (p <= 0.0) return 1;
-    if (p >= 1.0) return max_iters;
-    const double k = ceil(log1mc / log(p));
-    return k < (double)max_iters ? (int)k : max_iters;
-}
-
 // Hypotheses [256 (blockIdx.x + blk0), + 256) of pair blockIdx.z against correspondences [chunk blockIdx.y, + chunk).  The first 256 hypotheses of
 // every pair are scored first (blk0 = 0, bound = NULL); the later blocks run only where homog_bound_kernel left a bound above their first index.
 __global__ __launch_bounds__(256) void homog_score_kernel(HgArgs a, int blk0, const int* __restrict__ bound) {
     __shared__ unsigned stab[hg::NBINS];
     __shared__ float4 spt[hg::PTS_PER_WG];
     const int pair = blockIdx.z, tid = threadIdx.x;
-    const int n = a.counts ? min(a.counts[pair], a.cap) : a.n_const;
+    const int n = rs::pair_count(a, pair);
     const int c0 = blockIdx.y * a.chunk;
     const int it0 = (blockIdx.x + blk0) * hg::HYP_PER_WG;
     if (n < 4 || c0 >= n) return;
     if (bound && bound[pair] <= it0) return;
-    const PairPts pts(a, pair);
+    const rs::PairView pts(a, pair);
     const int c1 = min(c0 + a.chunk, n);
 #pragma unroll
     for (int k = 0; k < hg::NBINS / 256; ++k) stab[tid + 256 * k] = a.stab[tid + 256 * k];
 #pragma unroll
     for (int k = 0; k < hg::PTS_PER_WG / 256; ++k) {      // the chunk's correspondences: fetched (and de-referenced) once per workgroup
         const int i = c0 + tid + 256 * k;
-        float2 q0 = make_float2(0.f, 0.f), q1 = q0;
-        if (i < c1) pts.get(i, q0, q1);
-        spt[tid + 256 * k] = make_float4(q0.x, q0.y, q1.x, q1.y);
+        spt[tid + 256 * k] = i < c1 ? pts.get(i) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
     const int it = it0 + tid;
@@ -226,7 +172,7 @@ __global__ __launch_bounds__(256) void homog_score_kernel(HgArgs a, int blk0, co
         const float4 q = spt[i];                          // scheduler interleaves the fp64 chains of consecutive correspondences
         const double r2 = residual_sq(h, q.x, q.y, q.z, q.w);
         const bool near = r2 < a.tmax2;
-        const unsigned e = stab[bin_of(near ? r2 : 0.0, a.bin_scale)];
+        const unsigned e = stab[rs::bin_of(near ? r2 : 0.0, a.bin_scale)];
         s += near ? e : 0u;
         c += r2 < a.thr2 ? 1u : 0u;
     }
@@ -234,58 +180,17 @@ __global__ __launch_bounds__(256) void homog_score_kernel(HgArgs a, int blk0, co
     atomicAdd(a.hcnt + (size_t)pair * a.iters_pad + it, c);
 }
 
-// After the first 256 hypotheses: an upper bound of the index the sequential loop stops at = min over the records (strict prefix maxima of
-// the quality) among them of iterations_needed.  If the loop stops inside the first 256 the value does not matter (no later hypothesis is
-// visited); if it does not, every record among the first 256 is one the loop sees, so its own bound is <= this one.
+// After the first 256 hypotheses: the bound of rs::hypotheses_bound over the records (strict prefix maxima of the quality) among them
 __global__ __launch_bounds__(256) void homog_bound_kernel(HgArgs a, int* __restrict__ bound) {
-    __shared__ unsigned long long sc[256];
-    __shared__ int bmin;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = a.counts ? min(a.counts[pair], a.cap) : a.n_const;
-    const unsigned long long mine = tid < a.iters ? a.hscore[(size_t)pair * a.iters_pad + tid] : 0ull;
-    sc[tid] = mine;
-    if (tid == 0) bmin = a.iters;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (int j = 0; j < tid; ++j) before = sc[j] > before ? sc[j] : before;
-    if (n >= 4 && mine > before) atomicMin(&bmin, iterations_needed(a.hcnt[(size_t)pair * a.iters_pad + tid], n, a.log1mc, a.iters));
-    __syncthreads();
+    const int n = rs::pair_count(a, pair);
+    const bool has = n >= 4 && tid < a.iters;
+    const size_t h = (size_t)pair * a.iters_pad + tid;
+    const int bmin = rs::hypotheses_bound<4, false>(has, has ? a.hscore[h] : 0ull, has ? a.hcnt[h] : 0u, n, a.log1mc, a.iters);
     if (tid == 0) bound[pair] = bmin;
 }
 
 // ---- selection, refinement, mask --------------------------------------------------------------------------------------------------------
-// Totals of N per-thread values over the workgroup, every thread gets them; the order of the additions is fixed.  Through LDS as a transpose:
-// thread (k, j) adds 32 of the 256 entries of row k, thread k the 8 partial sums -- ~40 dependent additions and four barriers.  (A butterfly of
-// wave shuffles costs 6 steps x 2 ds_bpermute per value, each waited for: with it the select kernel took 76-84 us instead of 52.)
-constexpr int RED_PITCH = 257;
-template <int N>
-__device__ inline void block_sums(double (&v)[N], double* buf /* N * RED_PITCH + 9 * N doubles */) {
-    static_assert(N * 8 <= 256, "one thread per (row, segment)");
-    const int tid = threadIdx.x;
-    double* part = buf + N * RED_PITCH;
-    double* tot = part + N * 8;
-    __syncthreads();                                       // buf free (previous use)
-#pragma unroll
-    for (int k = 0; k < N; ++k) buf[k * RED_PITCH + tid] = v[k];
-    __syncthreads();
-    if (tid < N * 8) {
-        const int k = tid >> 3, j = tid & 7;
-        const double* row = buf + k * RED_PITCH + j * 32;
-        double t = 0.0;
-#pragma unroll 8
-        for (int i = 0; i < 32; ++i) t += row[i];
-        part[tid] = t;
-    }
-    __syncthreads();
-    if (tid < N) {
-        const double* q = part + tid * 8;
-        tot[tid] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = tot[k];
-}
-
 // Solve the 8x8 normal equations of the weighted inhomogeneous DLT (unknowns a = h00 h01 h02, b = h10 h11 h12, c = h20 h21; h22 = 1) from the 23 sums.
 // The matrix is [[P 0 Cu] [0 P Cv] [Cu' Cv' R]] with one 3x3 block P = sum w p p' for both rows: Cholesky of P once, the 2x2 Schur complement
 // S = R - Xu'Xu - Xv'Xv (X = L^-1 C) for c, back-substitution for a and b -- the block form of the dense 8x8 Cholesky solve (5 square roots
@@ -354,8 +259,8 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
     __shared__ unsigned long long sc_sh;
     __shared__ unsigned cnt_sh;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = a.counts ? min(a.counts[pair], a.cap) : a.n_const;
-    const PairPts pts(a, pair);
+    const int n = rs::pair_count(a, pair);
+    const rs::PairView pts(a, pair);
     unsigned char* mask = a.mask + (size_t)pair * a.cap;
     int32_t* info = a.info + pair * 8;
     double* Hout = a.H + pair * 9;
@@ -372,7 +277,7 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
             for (; it < a.iters && it < k_stop; ++it) {
                 if (hs[it] > best_s) {
                     best = it; best_s = hs[it];
-                    const int need = iterations_needed(hc[it], n, a.log1mc, a.iters);
+                    const int need = rs::iterations_needed<4>(hc[it], n, a.log1mc, a.iters);
                     k_stop = need < k_stop ? need : k_stop;
                 }
             }
@@ -389,44 +294,20 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
     const int best = sel[0], iters_run = sel[1];
     double* red = reinterpret_cast<double*>(lds_raw);       // the score list is dead: its LDS is the reduction buffer from here on
     if (best < 0) {
-        for (int i = tid; i < a.cap; i += 256) mask[i] = 0;
+        rs::write_nothing_found(mask, a.cap, info, iters_run, n);
         if (tid < 9) Hout[tid] = 0.0;
-        if (tid < 8) info[tid] = tid == 2 ? iters_run : (tid == 1 ? -1 : (tid == 5 ? n : 0));
         return;
     }
     // ---- the first SEL_CACHE correspondences stay in LDS for all passes (every pass otherwise pays the index -> key-point round trip
     // again: ~1.5 us each, nine passes); longer lists re-read their tail
     float4* spt = reinterpret_cast<float4*>(lds_raw + a.sel_cache_off);
-    for (int i = tid; i < min(n, hg::SEL_CACHE); i += 256) {
-        float2 q0, q1;
-        pts.get(i, q0, q1);
-        spt[i] = make_float4(q0.x, q0.y, q1.x, q1.y);
-    }
+    for (int i = tid; i < min(n, hg::SEL_CACHE); i += 256) spt[i] = pts.get(i);
     __syncthreads();
-    auto for_each = [&](auto&& f) {                        // f(i, (x0, y0, x1, y1)) for this thread's correspondences tid, tid + 256, ...
-        for (int i = tid; i < n; i += 256) {
-            float4 q;
-            if (i < hg::SEL_CACHE) q = spt[i];
-            else {
-                float2 q0, q1;
-                pts.get(i, q0, q1);
-                q = make_float4(q0.x, q0.y, q1.x, q1.y);
-            }
-            f(i, q);
-        }
-    };
+    auto for_each = [&](auto&& f) { rs::for_each_cached(spt, n, [&](int i) { return pts.get(i); }, f); };
     // ---- Hartley normalisation of both point sets (conditioning of the normal equations only)
-    double c[4] = {0, 0, 0, 0};
-    for_each([&](int, const float4& q) { c[0] += q.x; c[1] += q.y; c[2] += q.z; c[3] += q.w; });
-    block_sums(c, red);
-    const double cx0 = c[0] / n, cy0 = c[1] / n, cx1 = c[2] / n, cy1 = c[3] / n;
-    double dd[2] = {0, 0};
-    for_each([&](int, const float4& q) {
-        const double ax = q.x - cx0, ay = q.y - cy0, bx = q.z - cx1, by = q.w - cy1;
-        dd[0] += sqrt(ax * ax + ay * ay); dd[1] += sqrt(bx * bx + by * by);
-    });
-    block_sums(dd, red);
-    const double s0 = dd[0] > 0 ? 1.41421356237309504880 / (dd[0] / n) : 1.0, s1 = dd[1] > 0 ? 1.41421356237309504880 / (dd[1] / n) : 1.0;
+    double nt[6];
+    rs::hartley_conditioning(for_each, (double)n, red, nt);
+    const double cx0 = nt[0], cy0 = nt[1], s0 = nt[2], cx1 = nt[3], cy1 = nt[4], s1 = nt[5];
 
     // ---- sigma-consensus++: re-weighted least squares while the quality rises
     double hcur[9], hbest[9];
@@ -444,7 +325,7 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
         for_each([&](int, const float4& p) {
             const double r2 = residual_sq(hcur, p.x, p.y, p.z, p.w);
             if (r2 < a.tmax2) {
-                const int b = bin_of(r2, a.bin_scale);
+                const int b = rs::bin_of(r2, a.bin_scale);
                 sc += a.stab[b];
                 const double w = a.wtab[b];
                 const double x = (p.x - cx0) * s0, y = (p.y - cy0) * s0, u = (p.z - cx1) * s1, v = (p.w - cy1) * s1;
@@ -456,7 +337,7 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
             }
         });
         atomicAdd(&sc_sh, sc);
-        block_sums(sm, red);                               // (its barriers also publish sc_sh)
+        rs::block_sums(sm, red);                               // (its barriers also publish sc_sh)
         const unsigned long long s_now = sc_sh;
         if (s_now <= s_best) break;
 #pragma unroll
@@ -497,7 +378,7 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
         mask[i] = mk;
         cn += mk;
     });
-    for (int i = (n > 0 ? n : 0) + tid; i < a.cap; i += 256) mask[i] = 0;      // rows beyond the pair's count
+    for (int i = n + tid; i < a.cap; i += 256) mask[i] = 0;      // rows beyond the pair's count
     atomicAdd(&cnt_sh, cn);
     __syncthreads();
     const int n_in = (int)cnt_sh;
@@ -512,8 +393,7 @@ __global__ __launch_bounds__(256) void homog_select_kernel(HgArgs a) {
         }
 #pragma unroll
         for (int k = 0; k < 9; ++k) Hout[k] = found ? hbest[k] / nrm : 0.0;
-        info[0] = found ? 1 : 0; info[1] = best; info[2] = iters_run; info[3] = n_in; info[4] = lo_accepted; info[5] = n;
-        info[6] = (int)(s_best & 0xffffffffull); info[7] = (int)(s_best >> 32);
+        rs::write_info(info, found, best, iters_run, n_in, lo_accepted, n, s_best);
     }
 }
 
@@ -534,7 +414,7 @@ int launch_find_homography(const float* p0, const float* p1, const int64_t* idx0
     a.iters_pad = ceil_div(max_iters, 256) * 256;
     const double t_max = hg::MAX_THR_FACTOR * thr;
     a.thr2 = thr * thr; a.tmax2 = t_max * t_max; a.bin_scale = hg::NBINS / (t_max * t_max); a.log1mc = log(1.0 - confidence);
-    a.seed = seed; a.sel_cache_off = 0; a.chunk = hg::PTS_PER_WG;
+    a.seed = seed; a.sel_cache_off = 0;
     unsigned char* w = static_cast<unsigned char*>(ws);
     a.wtab = reinterpret_cast<double*>(w); w += (size_t)hg::NBINS * 8;
     a.hscore = reinterpret_cast<unsigned long long*>(w); w += (size_t)P * a.iters_pad * 8;
@@ -546,16 +426,14 @@ int launch_find_homography(const float* p0, const float* p1, const int64_t* idx0
     int tg = ceil_div(nhyp, 256);
     tg = tg < hg::NBINS / 256 ? hg::NBINS / 256 : (tg > 1024 ? 1024 : tg);
     homog_tables_kernel<<<tg, 256, 0, st>>>(thr, a.stab, a.wtab, a.hscore, a.hcnt, nhyp);
-    // few pairs: smaller chunks of correspondences, so that one pair still spreads over the chip (integer scores: any split gives the same sums)
-    a.chunk = hg::PTS_PER_WG;
-    while (a.chunk > 64 && (long)P * ceil_div(cap, a.chunk) < 256) a.chunk >>= 1;
+    a.chunk = rs::score_chunk(P, cap);
     const int nblk = ceil_div(max_iters, hg::HYP_PER_WG), nch = ceil_div(cap, a.chunk);
     homog_score_kernel<<<dim3(1, nch, P), 256, 0, st>>>(a, 0, nullptr);
     if (nblk > 1) {
         homog_bound_kernel<<<P, 256, 0, st>>>(a, bound);
         homog_score_kernel<<<dim3(nblk - 1, nch, P), 256, 0, st>>>(a, 1, bound);
     }
-    const size_t red_bytes = (size_t)(hg::NSUM * RED_PITCH + 9 * hg::NSUM) * sizeof(double);
+    const size_t red_bytes = rs::block_sums_bytes(hg::NSUM);
     const size_t front = ((size_t)a.iters_pad * 12 > red_bytes ? (size_t)a.iters_pad * 12 : red_bytes) + 15 & ~(size_t)15;
     a.sel_cache_off = (int)front;
     const size_t lds = front + (size_t)hg::SEL_CACHE * sizeof(float4);

@@ -7,11 +7,10 @@
 // below on the host and holds it to that restatement bit for bit):
 //   * calibration: pixel (u, v) of pair p -> ((u - cx) / fx, (v - cy) / fy) in fp64 with pair p's PINHOLE intrinsics (K row-major 3x3);
 //     the threshold in these units is thr_n = max_epipolar_error / (0.5 (f0 + f1)), f = (fx + fy) / 2 of each camera -- our choice;
-//   * sample: 5 distinct correspondences; draw d of hypothesis `it` of pair p is the upper half of
-//     splitmix64-finaliser(seed + golden * (((p << 20) + it) * 16 + d + 1)) scaled to [0, n) (the construction of k_homography.hip);
-//     duplicates are redrawn, 16 draws at most; a sample that runs out of draws yields no model;
+//   * sample: 5 distinct correspondences, drawn as ransac_common.hpp states (splitmix64 of (seed, pair, hypothesis, draw); duplicates
+//     are redrawn, 16 draws at most; a sample that runs out of draws yields no model);
 //   * minimal solver (relpose_solve): null space of the 5x9 epipolar constraint matrix by Gauss-Jordan with partial pivoting (a pivot
-//     below PIVOT_EPS, or not finite: no model), its four vectors orthonormalised by modified Gram-Schmidt, E = x X + y Y + z Z + W; the 10 cubic constraints det E = 0 and (E E' - tr(E E')/2 I) E = 0
+//     below tv::PIVOT_EPS of twoview_math.hpp, or not finite: no model), its four vectors orthonormalised by modified Gram-Schmidt, E = x X + y Y + z Z + W; the 10 cubic constraints det E = 0 and (E E' - tr(E E')/2 I) E = 0
 //     (the trace constraint halved) as a 10x20 matrix in Nister's monomial order, Gauss-Jordan with partial pivoting on its first 10
 //     columns; B(z) from rows (x^2 z, x^2), (y^2 z, y^2), (xyz, xy); det B(z) (degree 10) made monic; real roots by a Sturm sequence
 //     (Cauchy bound, STURM_STEPS bisections on the root count per root, then SIGN_STEPS bisections on the sign of the polynomial, then
@@ -24,11 +23,11 @@
 //     floor(min(r^2, thr_n^2) / thr_n^2 * 2^20) summed as u64 (no summation order); inlier: r^2 < thr_n^2 (NaN: never); a hypothesis
 //     costs the minimum over its candidates (ties: the lower root);
 //   * stopping rule: hypotheses in order, a strictly lower cost makes a new best and bounds the loop by ceil(log(1 - p) / log(1 - w^5)),
-//     w = inlier ratio of the best; the loop stops at it >= max(min_iterations, bound);
+//     w = inlier ratio of the best; the loop stops at it >= max(min_iterations, bound) (rs::scan_stopping_rule of ransac_common.hpp);
 //   * refinement of the winner: up to 10 Gauss-Newton steps on R <- R cay(w), t <- normalise(t + d1 b1 + d2 b2) (b1, b2 from t and the
 //     axis of its smallest component) over the inliers, residual x2' E x1 weighted by 1 / (Sampson denominator) at the step's start,
 //     5x5 normal equations by Cholesky; a step is kept only if it strictly lowers the integer cost, the first rejected step ends it;
-//     the sums are fixed-order block reductions (the restatement repeats that order), so the refined pose is reproducible too;
+//     the sums are fixed-order block reductions (rs::block_sums; the restatement repeats that order), so the refined pose is reproducible too;
 //   * mask: r^2 < thr_n^2 under the final pose; found = at least 5 inliers; R, t (unit), E = [t]x R, mask: zeros when not found.
 //
 // What makes it a device algorithm is what made the homography one: hypothesis `it` is a function of (seed, pair, it) alone, so every
@@ -49,23 +48,24 @@
 //   relpose_bound_kernel  : the bound the loop reaches from the records among the first 256; the later blocks are solved and scored
 //                           only below max(min_iterations, bound)
 //   relpose_select_kernel : one workgroup per pair: stopping rule over the cost list (tiles in LDS), refinement, mask, outputs
-#include "kernels.hpp"
+#include "ransac_common.hpp"
+#include "twoview_math.hpp"
 
 #pragma clang fp contract(off)
 
 namespace xfh {
 namespace rp {
-constexpr int MAX_DRAWS = 16, LO_ITERS = 10, MAX_ITERS = 16384, MAX_CAND = 10;
-constexpr int SLICE = 280, SOLVE_WG = 64, HYP_PER_WG = 256, PTS_PER_WG = 512;
-constexpr int SEL_TILE = 2048, SEL_CACHE = 2048, NSUM = 20;
+using rs::HYP_PER_WG, rs::PTS_PER_WG, rs::SEL_TILE, rs::SEL_CACHE;
+constexpr int LO_ITERS = 10, MAX_ITERS = 16384, MAX_CAND = 10;
+constexpr int SLICE = 280, SOLVE_WG = 64, NSUM = 20;
 }  // namespace rp
 
-// ---- solver begin (host-compilable: tests/test_relpose_emulated.py slices it out and drops the __device__ qualifiers) ----
+// ---- solver begin (host-compilable: tests/test_relpose_emulated.py slices it out behind the slice of twoview_math.hpp and drops the
+// __device__ qualifiers) ----
 namespace rp {
 constexpr int STURM_STEPS = 48, SIGN_STEPS = 48, NEWTON_STEPS = 4;
 constexpr int CAND_DOUBLES = 12;             // R (row-major) + t of one candidate pose
 }  // namespace rp
-constexpr double RP_PIVOT_EPS = 1e-12;
 // slice layout (fp64 elements): [0, 200) the 10x20 matrix (first the 5x9 one, last the Sturm sequence), [200, 260) the six quadratic
 // entries of E E' - tr/2 I, [260, 280) the sample: x1[5] y1[5] x2[5] y2[5]
 constexpr int RP_M = 0, RP_Q = 200, RP_PTS = 260;
@@ -76,19 +76,6 @@ constexpr int RP_QL[10][4] = {{0, 2, 4, 5}, {3, 1, 6, 7}, {10, 13, 16, 17}, {2, 
                               {8, 6, 13, 14}, {5, 9, 11, 12}, {9, 7, 14, 15}, {11, 14, 17, 18}, {12, 15, 18, 19}};
 constexpr int RP_SYM[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
 
-template <int ST>
-struct RpSlice {
-    double* b;
-    __device__ inline double& operator[](int k) const { return b[k * ST]; }
-};
-
-__device__ inline bool rp_finite(double v) { return v - v == 0.0; }
-__device__ inline void rp_cross(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ inline double rp_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 // E = [t]x R
 __device__ inline void rp_pose_E(const double* R, const double* t, double* E) {
     for (int j = 0; j < 3; ++j) {
@@ -97,47 +84,10 @@ __device__ inline void rp_pose_E(const double* R, const double* t, double* E) {
         E[6 + j] = t[0] * R[3 + j] - t[1] * R[j];
     }
 }
-// Sampson error of x1 = (a, b, 1), x2 = (c, d, 1)
-__device__ inline double rp_sampson(const double* E, double a, double b, double c, double d) {
-    const double e0 = (E[0] * a + E[1] * b) + E[2], e1 = (E[3] * a + E[4] * b) + E[5], e2 = (E[6] * a + E[7] * b) + E[8];
-    const double f0 = (E[0] * c + E[3] * d) + E[6], f1 = (E[1] * c + E[4] * d) + E[7];
-    const double num = (c * e0 + d * e1) + e2;
-    const double den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1;
-    return num * num / den;
-}
 // MSAC cost in 2^-20 units of thr2; NaN counts as the cap
 __device__ inline unsigned rp_cost(double r2, double thr2) {
     const double m = r2 < thr2 ? r2 : thr2;
     return (unsigned)floor(m / thr2 * 1048576.0);
-}
-// Gauss-Jordan with partial pivoting on the first `piv` columns of a rows x cols matrix at S[base + r * cols + c]; false if degenerate
-template <class S>
-__device__ inline bool rp_gauss_jordan(S s, int base, int rows, int cols) {
-    for (int c = 0; c < rows; ++c) {
-        int p = c;
-        double best = fabs(s[base + c * cols + c]);
-        for (int r = c + 1; r < rows; ++r) {
-            const double v = fabs(s[base + r * cols + c]);
-            if (v > best) { best = v; p = r; }
-        }
-        if (!(best >= RP_PIVOT_EPS)) return false;
-        if (p != c)
-            for (int j = c; j < cols; ++j) {
-                const double tmp = s[base + c * cols + j];
-                s[base + c * cols + j] = s[base + p * cols + j];
-                s[base + p * cols + j] = tmp;
-            }
-        const double inv = 1.0 / s[base + c * cols + c];
-        for (int j = c + 1; j < cols; ++j) s[base + c * cols + j] = s[base + c * cols + j] * inv;
-        s[base + c * cols + c] = 1.0;
-        for (int r = 0; r < rows; ++r) {
-            if (r == c) continue;
-            const double f = s[base + r * cols + c];
-            for (int j = c + 1; j < cols; ++j) s[base + r * cols + j] = s[base + r * cols + j] - f * s[base + c * cols + j];
-            s[base + r * cols + c] = 0.0;
-        }
-    }
-    return true;
 }
 __device__ inline double rp_horner(const double* a, int deg, double x) {
     double v = a[deg];
@@ -166,12 +116,6 @@ __device__ inline int rp_sturm_changes(S s, double x) {
     }
     return n;
 }
-// poly product c[0..da+db] = a * b (ascending powers), accumulated in the order i, j
-__device__ inline void rp_pmul(const double* a, int da, const double* b, int db, double* c) {
-    for (int k = 0; k <= da + db; ++k) c[k] = 0.0;
-    for (int i = 0; i <= da; ++i)
-        for (int j = 0; j <= db; ++j) c[i + j] = c[i + j] + a[i] * b[j];
-}
 // candidate poses of the sample in S[RP_PTS ..]: out[12 c ..] = R (row-major), t (unit); returns their number (0: no model)
 template <class S>
 __device__ inline int relpose_solve(S s, double* out) {
@@ -183,7 +127,7 @@ __device__ inline int relpose_solve(S s, double* out) {
 #pragma unroll
         for (int j = 0; j < 9; ++j) s[RP_M + 9 * k + j] = r[j];
     }
-    if (!rp_gauss_jordan(s, RP_M, 5, 9)) return 0;
+    if (!tv::gauss_jordan(s, RP_M, 5, 9)) return 0;
     // null basis v_k = (-C[:, k], e_k) of the reduced matrix, orthonormalised by modified Gram-Schmidt (k = 0..3 in order, sums over the
     // 9 entries in index order): the raw basis is badly scaled for a sizeable fraction of samples, which the degree-10 polynomial inherits
     // (the true z stops being one of its roots); E entry m is then the linear polynomial (x, y, z, 1) -> e[m][0..3] = v_0..3[m]
@@ -276,7 +220,7 @@ __device__ inline int relpose_solve(S s, double* out) {
                     for (int b = 0; b < 4; ++b) s[RP_M + 20 * row + RP_QL[a][b]] = s[RP_M + 20 * row + RP_QL[a][b]] + qa * e[3 * k + j][b];
                 }
         }
-    if (!rp_gauss_jordan(s, RP_M, 10, 20)) return 0;
+    if (!tv::gauss_jordan(s, RP_M, 10, 20)) return 0;
     // ---- B(z): rows k = r4 - z r5, l = r6 - z r7, m = r8 - z r9 of the tail (xz2 xz x yz2 yz y z3 z2 z 1); x, y parts degree 3, constant 4
     double bx[3][4], by[3][4], b1[3][5];
 #pragma unroll
@@ -290,26 +234,26 @@ __device__ inline int relpose_solve(S s, double* out) {
     double p[11];
     {
         double t1[8], t2[8], c1[8], c2[8], c3[7], w[11];
-        rp_pmul(by[1], 3, b1[2], 4, t1); rp_pmul(b1[1], 4, by[2], 3, t2);
+        tv::pmul(by[1], 3, b1[2], 4, t1); tv::pmul(b1[1], 4, by[2], 3, t2);
 #pragma unroll
         for (int k = 0; k < 8; ++k) c1[k] = t1[k] - t2[k];
-        rp_pmul(bx[1], 3, b1[2], 4, t1); rp_pmul(b1[1], 4, bx[2], 3, t2);
+        tv::pmul(bx[1], 3, b1[2], 4, t1); tv::pmul(b1[1], 4, bx[2], 3, t2);
 #pragma unroll
         for (int k = 0; k < 8; ++k) c2[k] = t1[k] - t2[k];
-        rp_pmul(bx[1], 3, by[2], 3, t1); rp_pmul(by[1], 3, bx[2], 3, t2);
+        tv::pmul(bx[1], 3, by[2], 3, t1); tv::pmul(by[1], 3, bx[2], 3, t2);
 #pragma unroll
         for (int k = 0; k < 7; ++k) c3[k] = t1[k] - t2[k];
-        rp_pmul(bx[0], 3, c1, 7, p);
-        rp_pmul(by[0], 3, c2, 7, w);
+        tv::pmul(bx[0], 3, c1, 7, p);
+        tv::pmul(by[0], 3, c2, 7, w);
 #pragma unroll
         for (int k = 0; k < 11; ++k) p[k] = p[k] - w[k];
-        rp_pmul(b1[0], 4, c3, 6, w);
+        tv::pmul(b1[0], 4, c3, 6, w);
 #pragma unroll
         for (int k = 0; k < 11; ++k) p[k] = p[k] + w[k];
     }
     // ---- Sturm sequence of the monic polynomial into the M area
     const double lead = p[10];
-    if (!(fabs(lead) > 0.0) || !rp_finite(lead)) return 0;
+    if (!(fabs(lead) > 0.0) || !tv::is_finite(lead)) return 0;
     double bound = 0.0;
 #pragma unroll
     for (int k = 0; k < 11; ++k) {
@@ -321,7 +265,7 @@ __device__ inline int relpose_solve(S s, double* out) {
     bound = 1.0 + bound;
 #pragma unroll
     for (int k = 0; k < 10; ++k) s[RP_M + 11 + k] = (double)(k + 1) * s[RP_M + k + 1];
-    bool fin = rp_finite(bound);
+    bool fin = tv::is_finite(bound);
     {
         int oa = RP_M, ob = RP_M + 11;                     // a: degree d + 1, b: degree d
         for (int d = 9; d >= 1; --d) {
@@ -335,7 +279,7 @@ __device__ inline int relpose_solve(S s, double* out) {
             }
             oa = ob; ob = oc;
         }
-        for (int k = 0; k < 66; ++k) fin = fin && rp_finite(s[RP_M + k]);
+        for (int k = 0; k < 66; ++k) fin = fin && tv::is_finite(s[RP_M + k]);
     }
     if (!fin) return 0;
     const int v_lo = rp_sturm_changes(s, -bound), v_hi = rp_sturm_changes(s, bound);
@@ -368,7 +312,7 @@ __device__ inline int relpose_solve(S s, double* out) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) { rows[r][0] = rp_horner(bx[r], 3, z); rows[r][1] = rp_horner(by[r], 3, z); rows[r][2] = rp_horner(b1[r], 4, z); }
         double cr[3][3];
-        rp_cross(rows[0], rows[1], cr[0]); rp_cross(rows[0], rows[2], cr[1]); rp_cross(rows[1], rows[2], cr[2]);
+        tv::cross3(rows[0], rows[1], cr[0]); tv::cross3(rows[0], rows[2], cr[1]); tv::cross3(rows[1], rows[2], cr[2]);
         const double a0 = fabs(cr[0][2]), a1 = fabs(cr[1][2]), a2 = fabs(cr[2][2]);
         const int pick = a2 > (a1 > a0 ? a1 : a0) ? 2 : (a1 > a0 ? 1 : 0);
         const double pm = pick == 0 ? a0 : (pick == 1 ? a1 : a2);
@@ -377,9 +321,9 @@ __device__ inline int relpose_solve(S s, double* out) {
         if (!(pm > 0.0)) continue;
         const double x = v[0] / v[2], y = v[1] / v[2];
         double E[9];
-        bool ok = rp_finite(x) && rp_finite(y);
+        bool ok = tv::is_finite(x) && tv::is_finite(y);
 #pragma unroll
-        for (int m = 0; m < 9; ++m) { E[m] = ((x * e[m][0] + y * e[m][1]) + z * e[m][2]) + e[m][3]; ok = ok && rp_finite(E[m]); }
+        for (int m = 0; m < 9; ++m) { E[m] = ((x * e[m][0] + y * e[m][1]) + z * e[m][2]) + e[m][3]; ok = ok && tv::is_finite(E[m]); }
         if (!ok) continue;
         // ---- decomposition
         double s2 = 0.0;
@@ -388,8 +332,8 @@ __device__ inline int relpose_solve(S s, double* out) {
         s2 = s2 * 0.5;
         double c01[3], c02[3], c12[3];
         const double k0[3] = {E[0], E[3], E[6]}, k1[3] = {E[1], E[4], E[7]}, k2[3] = {E[2], E[5], E[8]};     // columns: t' E = 0
-        rp_cross(k0, k1, c01); rp_cross(k0, k2, c02); rp_cross(k1, k2, c12);
-        const double n01 = rp_dot(c01, c01), n02 = rp_dot(c02, c02), n12 = rp_dot(c12, c12);
+        tv::cross3(k0, k1, c01); tv::cross3(k0, k2, c02); tv::cross3(k1, k2, c12);
+        const double n01 = tv::dot3(c01, c01), n02 = tv::dot3(c02, c02), n12 = tv::dot3(c12, c12);
         const int tp = n12 > (n02 > n01 ? n02 : n01) ? 2 : (n02 > n01 ? 1 : 0);
         const double nt = tp == 0 ? n01 : (tp == 1 ? n02 : n12);
         double tc[3];
@@ -399,7 +343,7 @@ __device__ inline int relpose_solve(S s, double* out) {
         const double tn = sqrt(nt), sc = sqrt(s2);
         const double t[3] = {tc[0] / tn, tc[1] / tn, tc[2] / tn};
         double cof[9], te[9], Ra[9], Rb[9];
-        rp_cross(E + 3, E + 6, cof); rp_cross(E + 6, E, cof + 3); rp_cross(E, E + 3, cof + 6);
+        tv::cross3(E + 3, E + 6, cof); tv::cross3(E + 6, E, cof + 3); tv::cross3(E, E + 3, cof + 6);
         rp_pose_E(E, t, te);                               // [t]x E (the same products as [t]x R)
 #pragma unroll
         for (int m = 0; m < 9; ++m) {
@@ -421,8 +365,8 @@ __device__ inline int relpose_solve(S s, double* out) {
                 const double x2[3] = {s[RP_PTS + 10 + i], s[RP_PTS + 15 + i], 1.0};
                 const double rx[3] = {(R[0] * x1[0] + R[1] * x1[1]) + R[2], (R[3] * x1[0] + R[4] * x1[1]) + R[5], (R[6] * x1[0] + R[7] * x1[1]) + R[8]};
                 double u[3], w[3], g[3], h[3];
-                rp_cross(x2, rx, u); rp_cross(x2, tq, w); rp_cross(rx, tq, g); rp_cross(rx, x2, h);
-                front = front && (-rp_dot(w, u) > 0.0) && (rp_dot(g, h) > 0.0);
+                tv::cross3(x2, rx, u); tv::cross3(x2, tq, w); tv::cross3(rx, tq, g); tv::cross3(rx, x2, h);
+                front = front && (-tv::dot3(w, u) > 0.0) && (tv::dot3(g, h) > 0.0);
             }
             chosen = chosen < 0 && front ? q : chosen;
         }
@@ -463,15 +407,11 @@ struct RpArgs {
     int32_t* info;
 };
 
+// the pair's correspondences in normalised coordinates: the view of ransac_common.hpp and the calibration
 struct RpPair {
-    const float* p0;
-    const float* p1;
-    const int64_t* i0;
-    const int64_t* i1;
+    rs::PairView pts;
     double fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1, thr2;
-    __device__ RpPair(const RpArgs& a, int pair)
-        : p0(a.p0 + (size_t)pair * a.kcap * 2), p1(a.p1 + (size_t)pair * a.kcap * 2), i0(a.idx0 ? a.idx0 + (size_t)pair * a.cap : nullptr),
-          i1(a.idx1 ? a.idx1 + (size_t)pair * a.cap : nullptr) {
+    __device__ RpPair(const RpArgs& a, int pair) : pts(a, pair) {
         const double* k0 = a.K0 + (size_t)pair * 9;
         const double* k1 = a.K1 + (size_t)pair * 9;
         fx0 = k0[0]; cx0 = k0[2]; fy0 = k0[4]; cy0 = k0[5];
@@ -481,32 +421,13 @@ struct RpPair {
     }
     // normalised coordinates (x1, y1, x2, y2) of correspondence i
     __device__ inline double4 get(int i) const {
-        const size_t r0 = i0 ? (size_t)i0[i] : (size_t)i, r1 = i1 ? (size_t)i1[i] : (size_t)i;
-        const float2 q0 = *reinterpret_cast<const float2*>(p0 + 2 * r0);
-        const float2 q1 = *reinterpret_cast<const float2*>(p1 + 2 * r1);
-        return make_double4(((double)q0.x - cx0) / fx0, ((double)q0.y - cy0) / fy0, ((double)q1.x - cx1) / fx1, ((double)q1.y - cy1) / fy1);
+        const float4 q = pts.get(i);
+        return make_double4(((double)q.x - cx0) / fx0, ((double)q.y - cy0) / fy0, ((double)q.z - cx1) / fx1, ((double)q.w - cy1) / fy1);
     }
 };
 
-__device__ inline int rp_count(const RpArgs& a, int pair) { return a.counts ? min(max(a.counts[pair], 0), a.cap) : a.n_const; }
-
-__device__ inline unsigned long long rp_mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ inline int rp_draw(unsigned long long seed, int pair, int it, int draw, int n) {
-    const unsigned long long counter = ((unsigned long long)pair * (1ull << 20) + (unsigned long long)it) * rp::MAX_DRAWS + (unsigned long long)draw;
-    const unsigned long long h = rp_mix64(seed + 0x9e3779b97f4a7c15ull * (counter + 1ull));
-    return (int)(((h >> 32) * (unsigned long long)n) >> 32);
-}
-
 __global__ __launch_bounds__(256) void relpose_zero_kernel(RpArgs a, size_t nhyp) {
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nhyp; j += (size_t)gridDim.x * 256) {
-        a.ncand[j] = 0;
-#pragma unroll
-        for (int c = 0; c < rp::MAX_CAND; ++c) { a.hcost[j * rp::MAX_CAND + c] = 0ull; a.hcnt[j * rp::MAX_CAND + c] = 0u; }
-    }
+    rs::zero_hypotheses<rp::MAX_CAND>(a.ncand, a.hcost, a.hcnt, nhyp);
 }
 
 // hypotheses [it_base + 64 blockIdx.x, + 64) of pair blockIdx.y; only below the pair's bound when `use_bound`
@@ -514,23 +435,13 @@ __global__ __launch_bounds__(64) void relpose_solve_kernel(RpArgs a, int it_base
     extern __shared__ __attribute__((aligned(16))) double rp_lds[];
     const int pair = blockIdx.y, tid = threadIdx.x;
     const int it = it_base + blockIdx.x * rp::SOLVE_WG + tid;
-    const int n = rp_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     if (n < 5 || it >= a.iters) return;
     if (use_bound && a.bound[pair] <= it) return;
     const RpPair pp(a, pair);
-    int idx[5] = {-1, -1, -1, -1, -1}, slot = 0;
-#pragma unroll
-    for (int d = 0; d < rp::MAX_DRAWS; ++d) {
-        const int c = rp_draw(a.seed, pair, it, d, n);
-        const bool dup = (slot > 0 && c == idx[0]) || (slot > 1 && c == idx[1]) || (slot > 2 && c == idx[2]) || (slot > 3 && c == idx[3]);
-        if (slot < 5 && !dup) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) idx[k] = slot == k ? c : idx[k];
-            ++slot;
-        }
-    }
-    if (slot < 5) return;
-    RpSlice<rp::SOLVE_WG> s{rp_lds + tid};
+    int idx[5] = {-1, -1, -1, -1, -1};
+    if (!rs::sample_distinct(a.seed, pair, it, n, idx)) return;
+    tv::Slice<rp::SOLVE_WG> s{rp_lds + tid};
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const double4 q = pp.get(idx[k]);
@@ -544,7 +455,7 @@ __global__ __launch_bounds__(64) void relpose_solve_kernel(RpArgs a, int it_base
 __global__ __launch_bounds__(256) void relpose_score_kernel(RpArgs a, int blk0, int use_bound) {
     __shared__ double4 spt[rp::PTS_PER_WG];
     const int pair = blockIdx.z, tid = threadIdx.x;
-    const int n = rp_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     const int c0 = blockIdx.y * a.chunk;
     const int it0 = (blockIdx.x + blk0) * rp::HYP_PER_WG;
     if (n < 5 || c0 >= n) return;
@@ -571,7 +482,7 @@ __global__ __launch_bounds__(256) void relpose_score_kernel(RpArgs a, int blk0, 
 #pragma unroll 4
         for (int i = 0; i < m; ++i) {
             const double4 q = spt[i];
-            const double r2 = rp_sampson(E, q.x, q.y, q.z, q.w);
+            const double r2 = tv::sampson(E, q.x, q.y, q.z, q.w);
             sc += rp_cost(r2, pp.thr2);
             cnt += r2 < pp.thr2 ? 1u : 0u;
         }
@@ -580,80 +491,20 @@ __global__ __launch_bounds__(256) void relpose_score_kernel(RpArgs a, int blk0, 
     }
 }
 
-// iterations the loop still needs once a model with `inliers` of n is the best one
-__device__ inline int rp_iterations_needed(unsigned inliers, int n, double log1mp, int max_iters) {
-    const double w = (double)inliers / (double)n;
-    const double p = 1.0 - ((((w * w) * w) * w) * w);
-    if (p <= 0.0) return 1;
-    if (p >= 1.0) return max_iters;
-    const double k = ceil(log1mp / log(p));
-    return k < (double)max_iters ? (int)k : max_iters;
-}
-// hypothesis cost (minimum over its candidates, the lower index on ties) and that candidate's inlier count; false: no model
-__device__ inline bool rp_hyp_cost(const RpArgs& a, size_t h, unsigned long long& cost, unsigned& cnt, int& cand) {
-    const int nc = a.ncand[h];
-    if (nc <= 0) return false;
-    cost = a.hcost[h * rp::MAX_CAND];
-    cnt = a.hcnt[h * rp::MAX_CAND];
-    cand = 0;
-    for (int c = 1; c < nc; ++c) {
-        const unsigned long long v = a.hcost[h * rp::MAX_CAND + c];
-        if (v < cost) { cost = v; cnt = a.hcnt[h * rp::MAX_CAND + c]; cand = c; }
-    }
-    return true;
-}
-
-// After the first 256 hypotheses: the index below which the loop can still visit hypotheses = max(min_iters, min over the records among
-// them of the bound); see homog_bound_kernel for why the records of the first block bound the loop
+// After the first 256 hypotheses: the index below which the loop can still visit hypotheses = max(min_iters, rs::hypotheses_bound over
+// the records (strict prefix minima of the cost) among them); a hypothesis costs the minimum over its candidates (rs::hyp_best)
 __global__ __launch_bounds__(256) void relpose_bound_kernel(RpArgs a) {
-    __shared__ unsigned long long sc[256];
-    __shared__ int bmin;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = rp_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     unsigned long long cost = ~0ull;
     unsigned cnt = 0;
     int cand = 0;
-    const bool has = tid < a.iters && n >= 5 && rp_hyp_cost(a, (size_t)pair * a.iters_pad + tid, cost, cnt, cand);
-    sc[tid] = has ? cost : ~0ull;
-    if (tid == 0) bmin = a.iters;
-    __syncthreads();
-    unsigned long long before = ~0ull;
-    for (int j = 0; j < tid; ++j) before = sc[j] < before ? sc[j] : before;
-    if (has && cost < before) atomicMin(&bmin, rp_iterations_needed(cnt, n, a.log1mp, a.iters));
-    __syncthreads();
+    const bool has = tid < a.iters && n >= 5 && rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost, a.hcnt, (size_t)pair * a.iters_pad + tid, cost, cnt, cand);
+    const int bmin = rs::hypotheses_bound<5, true>(has, cost, cnt, n, a.log1mp, a.iters);
     if (tid == 0) a.bound[pair] = bmin > a.min_iters ? bmin : a.min_iters;
 }
 
 // ---- selection, refinement, mask --------------------------------------------------------------------------------------------------------
-// Totals of N per-thread values over the 256 threads in a fixed order (thread (k, j) adds 32 entries of row k, thread k the 8 partials)
-constexpr int RP_RED_PITCH = 257;
-template <int N>
-__device__ inline void rp_block_sums(double (&v)[N], double* buf /* N * RP_RED_PITCH + 9 * N doubles */) {
-    static_assert(N * 8 <= 256, "one thread per (row, segment)");
-    const int tid = threadIdx.x;
-    double* part = buf + N * RP_RED_PITCH;
-    double* tot = part + N * 8;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) buf[k * RP_RED_PITCH + tid] = v[k];
-    __syncthreads();
-    if (tid < N * 8) {
-        const int k = tid >> 3, j = tid & 7;
-        const double* row = buf + k * RP_RED_PITCH + j * 32;
-        double t = 0.0;
-        for (int i = 0; i < 32; ++i) t += row[i];
-        part[tid] = t;
-    }
-    __syncthreads();
-    if (tid < N) {
-        const double* q = part + tid * 8;
-        tot[tid] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = tot[k];
-}
-
 // one Gauss-Newton step from (R, t) with the 20 sums (H upper triangle row-major, then g); false if the normal equations are not positive
 __device__ inline bool rp_gn_update(const double (&sm)[rp::NSUM], const double* R, const double* t, const double* b1, const double* b2, double* Rn, double* tn) {
     double H[5][5], L[5][5], g[5], y[5], d[5];
@@ -697,11 +548,11 @@ __device__ inline bool rp_gn_update(const double (&sm)[rp::NSUM], const double* 
         for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (R[3 * i] * Cm[j] + R[3 * i + 1] * Cm[3 + j]) + R[3 * i + 2] * Cm[6 + j];
     double tv[3];
     for (int i = 0; i < 3; ++i) tv[i] = (t[i] + d[3] * b1[i]) + d[4] * b2[i];
-    const double nn = sqrt(rp_dot(tv, tv));
+    const double nn = sqrt(tv::dot3(tv, tv));
     for (int i = 0; i < 3; ++i) tn[i] = tv[i] / nn;
     bool fin = true;
-    for (int i = 0; i < 9; ++i) fin = fin && rp_finite(Rn[i]);
-    for (int i = 0; i < 3; ++i) fin = fin && rp_finite(tn[i]);
+    for (int i = 0; i < 9; ++i) fin = fin && tv::is_finite(Rn[i]);
+    for (int i = 0; i < 3; ++i) fin = fin && tv::is_finite(tn[i]);
     return fin;
 }
 // tangent basis of the unit vector t: b1 = normalise(t x e_k), k the axis of the smallest |t_k| (the first on ties), b2 = t x b1
@@ -711,84 +562,47 @@ __device__ inline void rp_tangent(const double* t, double* b1, double* b2) {
     if (fabs(t[2]) < fabs(t[k])) k = 2;
     const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
     double c[3];
-    rp_cross(t, ek, c);
-    const double nn = sqrt(rp_dot(c, c));
+    tv::cross3(t, ek, c);
+    const double nn = sqrt(tv::dot3(c, c));
     for (int i = 0; i < 3; ++i) b1[i] = c[i] / nn;
-    rp_cross(t, b1, b2);
+    tv::cross3(t, b1, b2);
 }
 
 __global__ __launch_bounds__(256) void relpose_select_kernel(RpArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ double pose_sh[12];
-    __shared__ int sel[4];
     __shared__ unsigned long long sc_sh;
     __shared__ unsigned cnt_sh;
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const int n = rp_count(a, pair);
+    const int n = rs::pair_count(a, pair);
     unsigned char* mask = a.mask + (size_t)pair * a.cap;
     int32_t* info = a.info + pair * 8;
 
     // ---- the stopping rule of the sequential loop, over tiles of the cost list
-    unsigned long long* tc = reinterpret_cast<unsigned long long*>(lds_raw);
-    unsigned* tn = reinterpret_cast<unsigned*>(lds_raw + (size_t)rp::SEL_TILE * 8);
-    int* tk = reinterpret_cast<int*>(lds_raw + (size_t)rp::SEL_TILE * 12);
-    if (tid == 0) { sel[0] = -1; sel[1] = 0; sel[2] = -1; sel[3] = a.iters; }
-    __shared__ unsigned long long best_sh;
-    __shared__ int stop_sh, done_sh;
-    if (tid == 0) { best_sh = ~0ull; stop_sh = a.iters; done_sh = n < 5 ? 1 : 0; }
-    __syncthreads();
-    for (int base = 0; base < a.iters; base += rp::SEL_TILE) {
-        if (done_sh) break;
-        for (int i = tid; i < rp::SEL_TILE; i += 256) {
-            const int it = base + i;
-            unsigned long long c = ~0ull;
-            unsigned k = 0;
-            int cd = -1;
-            if (it < a.iters && it < (stop_sh > a.min_iters ? stop_sh : a.min_iters) && !rp_hyp_cost(a, (size_t)pair * a.iters_pad + it, c, k, cd)) cd = -1;
-            tc[i] = c; tn[i] = k; tk[i] = cd;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int it = base;
-            int stop = stop_sh;
-            for (; it < a.iters && it < base + rp::SEL_TILE; ++it) {
-                if (it >= (stop > a.min_iters ? stop : a.min_iters)) { done_sh = 1; break; }
-                const int i = it - base;
-                if (tk[i] >= 0 && tc[i] < best_sh) {
-                    best_sh = tc[i]; sel[0] = it; sel[2] = tk[i];
-                    const int need = rp_iterations_needed(tn[i], n, a.log1mp, a.iters);
-                    stop = need < stop ? need : stop;
-                }
-            }
-            sel[1] = it;
-            stop_sh = stop;
-            if (it >= a.iters) done_sh = 1;
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    const int best = sel[0], iters_run = n < 5 ? 0 : sel[1];
-    if (best >= 0 && tid < 12) pose_sh[tid] = a.cand[(((size_t)pair * a.iters_pad + best) * rp::MAX_CAND + sel[2]) * rp::CAND_DOUBLES + tid];
+    int best, best_cand, iters_run;
+    rs::scan_stopping_rule<5, true>(lds_raw, n, a.iters, a.min_iters, a.log1mp,
+                                    [&](int it, unsigned long long& c, unsigned& k, int& cd) {
+                                        return rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost, a.hcnt, (size_t)pair * a.iters_pad + it, c, k, cd);
+                                    },
+                                    best, best_cand, iters_run);
+    if (best >= 0 && tid < 12) pose_sh[tid] = a.cand[(((size_t)pair * a.iters_pad + best) * rp::MAX_CAND + best_cand) * rp::CAND_DOUBLES + tid];
     __syncthreads();
     double* Rout = a.R + (size_t)pair * 9;
     double* tout = a.t + (size_t)pair * 3;
     double* Eout = a.E + (size_t)pair * 9;
     if (best < 0) {
-        for (int i = tid; i < a.cap; i += 256) mask[i] = 0;
+        rs::write_nothing_found(mask, a.cap, info, iters_run, n);
         if (tid < 9) { Rout[tid] = 0.0; Eout[tid] = 0.0; }
         if (tid < 3) tout[tid] = 0.0;
-        if (tid < 8) info[tid] = tid == 2 ? iters_run : (tid == 1 ? -1 : (tid == 5 ? n : 0));
         return;
     }
     const RpPair pp(a, pair);
     const double thr2 = pp.thr2;
     double* red = reinterpret_cast<double*>(lds_raw);         // the tiles are dead: reduction buffer from here on
-    double4* spt = reinterpret_cast<double4*>(lds_raw + (((size_t)rp::NSUM * RP_RED_PITCH + 9 * rp::NSUM) * 8 + 31 & ~(size_t)31));
+    double4* spt = reinterpret_cast<double4*>(lds_raw + (rs::block_sums_bytes(rp::NSUM) + 31 & ~(size_t)31));
     for (int i = tid; i < min(n, rp::SEL_CACHE); i += 256) spt[i] = pp.get(i);
     __syncthreads();
-    auto for_each = [&](auto&& f) {
-        for (int i = tid; i < n; i += 256) f(i, i < rp::SEL_CACHE ? spt[i] : pp.get(i));
-    };
+    auto for_each = [&](auto&& f) { rs::for_each_cached(spt, n, [&](int i) { return pp.get(i); }, f); };
     double Rc[9], tcur[3], Rb[9], tb[3];
     for (int k = 0; k < 9; ++k) { Rc[k] = pose_sh[k]; Rb[k] = Rc[k]; }
     for (int k = 0; k < 3; ++k) { tcur[k] = pose_sh[9 + k]; tb[k] = tcur[k]; }
@@ -825,7 +639,7 @@ __global__ __launch_bounds__(256) void relpose_select_kernel(RpArgs a) {
             }
         });
         atomicAdd(&sc_sh, sc);
-        rp_block_sums(sm, red);                              // (its barriers also publish sc_sh)
+        rs::block_sums(sm, red);                              // (its barriers also publish sc_sh)
         const unsigned long long c_now = sc_sh;
         if (step > 0 && !(c_now < c_best)) break;
         for (int k = 0; k < 9; ++k) Rb[k] = Rc[k];
@@ -846,18 +660,17 @@ __global__ __launch_bounds__(256) void relpose_select_kernel(RpArgs a) {
     if (tid == 0) cnt_sh = 0u;
     __syncthreads();
     unsigned cn = 0;
-    for_each([&](int, const double4& q) { cn += rp_sampson(Eb, q.x, q.y, q.z, q.w) < thr2 ? 1u : 0u; });
+    for_each([&](int, const double4& q) { cn += tv::sampson(Eb, q.x, q.y, q.z, q.w) < thr2 ? 1u : 0u; });
     atomicAdd(&cnt_sh, cn);
     __syncthreads();
     const int n_in = (int)cnt_sh;
     const bool found = n_in >= 5;
-    for_each([&](int i, const double4& q) { mask[i] = found && rp_sampson(Eb, q.x, q.y, q.z, q.w) < thr2 ? 1 : 0; });
+    for_each([&](int i, const double4& q) { mask[i] = found && tv::sampson(Eb, q.x, q.y, q.z, q.w) < thr2 ? 1 : 0; });
     for (int i = n + tid; i < a.cap; i += 256) mask[i] = 0;
     if (tid == 0) {
         for (int k = 0; k < 9; ++k) { Rout[k] = found ? Rb[k] : 0.0; Eout[k] = found ? Eb[k] : 0.0; }
         for (int k = 0; k < 3; ++k) tout[k] = found ? tb[k] : 0.0;
-        info[0] = found ? 1 : 0; info[1] = best; info[2] = iters_run; info[3] = n_in; info[4] = lo_accepted; info[5] = n;
-        info[6] = (int)(c_best & 0xffffffffull); info[7] = (int)(c_best >> 32);
+        rs::write_info(info, found, best, iters_run, n_in, lo_accepted, n, c_best);
     }
 }
 
@@ -885,8 +698,7 @@ int launch_estimate_relpose(const float* p0, const float* p1, const int64_t* idx
     a.R = R; a.t = t; a.E = E; a.mask = mask; a.info = info;
     size_t zg = (nhyp + 255) / 256;
     relpose_zero_kernel<<<(unsigned)(zg > 2048 ? 2048 : zg), 256, 0, st>>>(a, nhyp);
-    a.chunk = rp::PTS_PER_WG;
-    while (a.chunk > 64 && (long)P * ceil_div(cap, a.chunk) < 256) a.chunk >>= 1;
+    a.chunk = rs::score_chunk(P, cap);
     const int nblk = ceil_div(max_iters, rp::HYP_PER_WG), nch = ceil_div(cap, a.chunk);
     const size_t solve_lds = (size_t)rp::SLICE * rp::SOLVE_WG * sizeof(double);
     static AttrMask attr_solve = 0, attr_sel = 0;
@@ -899,7 +711,7 @@ int launch_estimate_relpose(const float* p0, const float* p1, const int64_t* idx
         relpose_solve_kernel<<<dim3(ceil_div(max_iters - rp::HYP_PER_WG, rp::SOLVE_WG), P), rp::SOLVE_WG, solve_lds, st>>>(a, rp::HYP_PER_WG, 1);
         relpose_score_kernel<<<dim3(nblk - 1, nch, P), 256, 0, st>>>(a, 1, 1);
     }
-    const size_t red = (((size_t)rp::NSUM * RP_RED_PITCH + 9 * rp::NSUM) * 8 + 31) & ~(size_t)31;
+    const size_t red = (rs::block_sums_bytes(rp::NSUM) + 31) & ~(size_t)31;
     const size_t tiles = (size_t)rp::SEL_TILE * 16;
     const size_t front = red > tiles ? red : tiles;
     const size_t lds = (front > red ? front : red) + (size_t)rp::SEL_CACHE * sizeof(double4);

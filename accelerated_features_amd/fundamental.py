@@ -11,13 +11,10 @@ oriented epipolar constraint, the MAGSAC++ quality and sigma-consensus++ refinem
 epipolar geometry, not in its random stream; parity with cv2 is not pinned.  A planar scene (or a pure rotation) does not determine F:
 use ``homography.find_homography`` there.  There is no CPU path: without the HIP library and a gfx950 device these functions raise.
 """
-import ctypes as C
-
-import numpy as np
 import torch
 
-from . import _lib
-from .pose import chunk_seed
+from . import _lib, _twoview
+from ._twoview import ptr as _ptr
 
 FM_7POINT = 1             # cv2.FM_7POINT: exactly 7 points, every real solution (up to 3, stacked)
 FM_8POINT = 2             # cv2.FM_8POINT: one least-squares fit on all points (at least 8)
@@ -26,16 +23,7 @@ METHODS = (FM_7POINT, FM_8POINT, USAC_MAGSAC)
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "score_lo", "score_hi")
 MAX_ITERATIONS = 16384                       # the kernel's limit; more is an error
 WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise _lib.XFeatHipError("fundamental matrix estimation needs an AMD MI355X (gfx950) GPU; no CPU fallback exists")
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+_WHAT = "fundamental matrix estimation"
 
 
 def _check_method(who, method):
@@ -58,26 +46,14 @@ def _run(who, pts0, pts1, index, counts, n_const, P, cap, method, ransac_thr, ma
         info[:, 1] = -1
     else:
         lib = _lib.load()
-        stream = torch.cuda.current_stream(dev)
         iters = int(max_iters) if method == USAC_MAGSAC else 1
-        per_pair = lib.xfh_fundamental_workspace_bytes(1, iters)
-        step = max(1, min(P, WORKSPACE_LIMIT // max(per_pair, 1)))
-        for a in range(0, P, step):
-            b = min(P, a + step)
-            n = b - a
-            ws = torch.empty(lib.xfh_fundamental_workspace_bytes(n, iters) + 256, dtype=torch.uint8, device=dev)
-            off = (-ws.data_ptr()) % 256
-            ws.record_stream(stream)
-            tail = (int(method), float(ransac_thr), iters, float(confidence), chunk_seed(seed, a), _ptr(F[a:b]), _ptr(mask[a:b]),
-                    _ptr(info[a:b]), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, C.c_void_p(stream.cuda_stream))
-            if index is None:
-                rc = lib.xfh_find_fundamental(_ptr(pts0[a:b]), _ptr(pts1[a:b]), _ptr(counts[a:b]) if counts is not None else None, n_const, n,
-                                              cap, *tail)
-            else:
-                idx0, idx1, kcap = index
-                rc = lib.xfh_find_fundamental_matches(_ptr(pts0[a:b]), _ptr(pts1[a:b]), kcap, _ptr(idx0[a:b]), _ptr(idx1[a:b]), _ptr(counts[a:b]),
-                                                      n, cap, *tail)
-            _lib.check(rc, who)
+        fn = lib.xfh_find_fundamental if index is None else lib.xfh_find_fundamental_matches
+
+        def call(a, b, *ws_and_stream):
+            return fn(*_twoview.list_args(pts0, pts1, index, counts, n_const, a, b, cap), int(method), float(ransac_thr), iters, float(confidence),
+                      _twoview.chunk_seed(seed, a), _ptr(F[a:b]), _ptr(mask[a:b]), _ptr(info[a:b]), *ws_and_stream)
+
+        _twoview.run_chunked(who, P, WORKSPACE_LIMIT, lambda n: lib.xfh_fundamental_workspace_bytes(n, iters), dev, call)
     return {'F': (F.view(P, 3, 3, 3) if method == FM_7POINT else F[:, 0].view(P, 3, 3)), 'inliers': mask, 'info': info}
 
 
@@ -91,16 +67,8 @@ def find_fundamental_batch(pts0, pts1, counts=None, ransac_thr=3.0, max_iters=10
     Returns a dict of CUDA tensors: 'F' (P,3,3) float64 ((P,3,3,3) for FM_7POINT: up to 3 solutions, zeros beyond info 'iters'),
     'inliers' (P,cap) uint8, 'info' (P,8) int32 (INFO_FIELDS; for FM_7POINT / FM_8POINT 'iters' holds the number of models).
     F is scaled to F[2,2] = 1 (unit Frobenius norm when |F[2,2]| <= FLT_EPSILON) and is zero where nothing was found.  Asynchronous."""
-    dev = pts0.device if torch.is_tensor(pts0) and pts0.is_cuda else _device()
-    pts0 = torch.as_tensor(pts0).to(dev).float().contiguous()
-    pts1 = torch.as_tensor(pts1).to(dev).float().contiguous()
-    if pts0.dim() != 3 or pts0.shape[2] != 2 or pts1.shape != pts0.shape:
-        raise RuntimeError('expected two (P, cap, 2) point tensors of the same shape')
+    pts0, pts1, counts, dev = _twoview.check_points(_WHAT, pts0, pts1, counts)
     P, cap = pts0.shape[0], pts0.shape[1]
-    if counts is not None:
-        counts = torch.as_tensor(counts).to(dev).to(torch.int32).contiguous()
-        if counts.shape != (P,):
-            raise RuntimeError('counts must have one entry per pair')
     return _run("xfh_find_fundamental", pts0, pts1, None, counts, cap, P, cap, method, ransac_thr, max_iters, confidence, seed, dev)
 
 
@@ -109,15 +77,7 @@ def find_fundamental_matches(kpts0, kpts1, idx0, idx1, n_matches, ransac_thr=3.0
     """The same estimator straight on the matcher's output: correspondence i of pair p is (kpts0[p, idx0[p, i]], kpts1[p, idx1[p, i]])
     for i < n_matches[p].  kpts (P,K,2) float32, idx (P,cap) int64, n_matches (P,) int32 CUDA tensors, as ``XFeat._detect_device`` and
     ``XFeat.match_pairs_device`` return them.  Same result dict as find_fundamental_batch."""
-    if not kpts0.is_cuda:
-        raise _lib.XFeatHipError("find_fundamental_matches works on device-resident match lists")
-    dev = kpts0.device
-    P, cap = idx0.shape
-    if kpts0.shape != kpts1.shape or kpts0.shape[0] != P or kpts0.shape[2] != 2 or idx1.shape != idx0.shape or n_matches.shape != (P,):
-        raise RuntimeError('expected kpts (P,K,2), idx (P,cap), n_matches (P,)')
-    for t, dt in ((kpts0, torch.float32), (kpts1, torch.float32), (idx0, torch.int64), (idx1, torch.int64), (n_matches, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError('find_fundamental_matches: contiguous float32 key-points, int64 indices, int32 counts expected')
+    dev, P, cap = _twoview.check_matches("find_fundamental_matches", kpts0, kpts1, idx0, idx1, n_matches)
     return _run("xfh_find_fundamental_matches", kpts0, kpts1, (idx0, idx1, kpts0.shape[1]), n_matches, 0, P, cap, method, ransac_thr,
                 max_iters, confidence, seed, dev)
 
@@ -134,9 +94,8 @@ def find_fundamental_mat(points1, points2, method=USAC_MAGSAC, ransacReprojThres
     (None, None) like cv2 when too few points are given or no model is found.  ``seed`` fixes the sample sequence (same arguments, same
     bits).  A planar scene does not determine F: use ``find_homography`` for it."""
     _check_method("find_fundamental_mat", method)
-    dev = _device()
-    a = torch.as_tensor(np.asarray(points1) if not torch.is_tensor(points1) else points1).reshape(-1, 2)
-    b = torch.as_tensor(np.asarray(points2) if not torch.is_tensor(points2) else points2).reshape(-1, 2)
+    dev = _twoview.device(_WHAT)
+    a, b = _twoview.as_points(points1), _twoview.as_points(points2)
     if a.shape != b.shape:
         raise RuntimeError('points1 and points2 must hold the same number of points')
     n = a.shape[0]

@@ -13,19 +13,13 @@ There is no CPU path: without the HIP library and a gfx950 device these function
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _twoview
+from ._twoview import ptr as _ptr
 
 USAC_MAGSAC = 38          # cv2.USAC_MAGSAC: accepted (and required) as ``method`` for signature compatibility
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "score_lo", "score_hi")
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise _lib.XFeatHipError("find_homography needs an AMD MI355X (gfx950) GPU; no CPU fallback exists")
-    return torch.device('cuda', torch.cuda.current_device())
 
 
 def _outputs(P, cap, dev):
@@ -41,10 +35,6 @@ def _workspace(lib, P, max_iters, dev):
     return ws, off
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def find_homography_batch(pts0, pts1, counts=None, ransac_thr=4.0, max_iters=700, confidence=0.995, seed=0):
     """P robust homographies in one call.
 
@@ -52,7 +42,7 @@ def find_homography_batch(pts0, pts1, counts=None, ransac_thr=4.0, max_iters=700
     counts     : (P,) int32 CUDA tensor, pair p uses its first counts[p] rows; None = all cap rows
     Returns a dict of CUDA tensors: 'H' (P,3,3) float64, 'inliers' (P,cap) uint8, 'info' (P,8) int32 (INFO_FIELDS).  Asynchronous.
     """
-    dev = pts0.device if pts0.is_cuda else _device()
+    dev = pts0.device if pts0.is_cuda else _twoview.device("find_homography")
     pts0 = pts0.to(dev).float().contiguous()
     pts1 = pts1.to(dev).float().contiguous()
     if pts0.dim() != 3 or pts0.shape[2] != 2 or pts1.shape != pts0.shape:
@@ -78,15 +68,7 @@ def find_homography_matches(kpts0, kpts1, idx0, idx1, n_matches, ransac_thr=4.0,
     (kpts0[p, idx0[p, i]], kpts1[p, idx1[p, i]]) for i < n_matches[p] -- ``points1 = kpts1[idx0]; points2 = kpts2[idx1]`` of
     realtime_demo.py:209-211.  kpts (P,K,2) float32, idx (P,cap) int64, n_matches (P,) int32: the CUDA tensors that
     ``XFeat._detect_device`` and ``XFeat.match_sets_device`` / ``match_pairs_device`` return.  Same result dict as find_homography_batch."""
-    dev = kpts0.device
-    if not kpts0.is_cuda:
-        raise _lib.XFeatHipError("find_homography_matches works on device-resident match lists")
-    P, cap = idx0.shape
-    if kpts0.shape != kpts1.shape or kpts0.shape[0] != P or kpts0.shape[2] != 2 or idx1.shape != idx0.shape or n_matches.shape != (P,):
-        raise RuntimeError('expected kpts (P,K,2), idx (P,cap), n_matches (P,)')
-    for t, dt in ((kpts0, torch.float32), (kpts1, torch.float32), (idx0, torch.int64), (idx1, torch.int64), (n_matches, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError('find_homography_matches: contiguous float32 key-points, int64 indices, int32 counts expected')
+    dev, P, cap = _twoview.check_matches("find_homography_matches", kpts0, kpts1, idx0, idx1, n_matches)
     H, mask, info = _outputs(P, cap, dev)
     lib = _lib.load()
     ws, off = _workspace(lib, P, max_iters, dev)
@@ -159,9 +141,8 @@ def find_homography(srcPoints, dstPoints, method=USAC_MAGSAC, ransacReprojThresh
     """
     if method != USAC_MAGSAC:
         raise _lib.XFeatHipError(f"find_homography: only cv2.USAC_MAGSAC ({USAC_MAGSAC}) is implemented, got method={method}")
-    dev = _device()
-    a = torch.as_tensor(np.asarray(srcPoints) if not torch.is_tensor(srcPoints) else srcPoints).reshape(-1, 2)
-    b = torch.as_tensor(np.asarray(dstPoints) if not torch.is_tensor(dstPoints) else dstPoints).reshape(-1, 2)
+    dev = _twoview.device("find_homography")
+    a, b = _twoview.as_points(srcPoints), _twoview.as_points(dstPoints)
     if a.shape != b.shape:
         raise RuntimeError('srcPoints and dstPoints must hold the same number of points')
     n = a.shape[0]

@@ -11,28 +11,19 @@ RANSAC, MSAC on the Sampson error, Gauss-Newton refinement), so the pose agrees 
 its random stream.  ``relative_pose_error``, ``pose_auc`` and ``pose_benchmark`` are the evaluation's metrics, written from their
 definitions.  There is no CPU path: without the HIP library and a gfx950 device the estimators raise.
 """
-import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _twoview
+from ._twoview import chunk_seed, ptr as _ptr           # chunk_seed is public here: pose.chunk_seed(seed, p) = the seed of pair p alone
 
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "cost_lo", "cost_hi")
 MAX_ITERATIONS = 16384                       # the kernel's limit; more is an error
 WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs
+_WHAT = "relative pose estimation"
 RANSAC_DEFAULTS = {"max_epipolar_error": 1.0, "success_prob": 0.99999, "min_iterations": 20, "max_iterations": 10000}
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise _lib.XFeatHipError("relative pose estimation needs an AMD MI355X (gfx950) GPU; no CPU fallback exists")
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _intrinsics(K, P, dev):
@@ -44,20 +35,9 @@ def _intrinsics(K, P, dev):
     return K.to(dev).contiguous()
 
 
-def _chunks(lib, P, max_iterations):
-    per_pair = lib.xfh_relpose_workspace_bytes(1, int(max_iterations))
-    step = max(1, min(P, WORKSPACE_LIMIT // max(per_pair, 1)))
-    return [(p, min(P, p + step)) for p in range(0, P, step)]
-
-
-def chunk_seed(seed, first_pair):
-    """The draws of pair p take (seed, p): a chunk that starts at pair `first_pair` sees its pairs as 0, 1, ..., so its seed is advanced by
-    the counter stride of `first_pair` pairs (golden * 2^24 per pair, mod 2^64) and the draws stay those of the whole batch."""
-    return (int(seed) + first_pair * 0x9e3779b97f4a7c15 * (1 << 24)) & ((1 << 64) - 1)
-
-
 def _run(who, pts0, pts1, index, counts, n_const, P, cap, K0, K1, max_epipolar_error, success_prob, min_iterations, max_iterations, seed, dev):
     """Shared driver: outputs, chunks of pairs under WORKSPACE_LIMIT, one library call per chunk.  index = (idx0, idx1, kcap) or None."""
+    K0, K1 = _intrinsics(K0, P, dev), _intrinsics(K1, P, dev)
     if not 1 <= int(max_iterations) <= MAX_ITERATIONS:
         raise _lib.XFeatHipError(f"{who}: max_iterations {max_iterations} outside [1, {MAX_ITERATIONS}]")
     R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
@@ -72,21 +52,14 @@ def _run(who, pts0, pts1, index, counts, n_const, P, cap, K0, K1, max_epipolar_e
         info[:, 1] = -1
         return out
     lib = _lib.load()
-    stream = torch.cuda.current_stream(dev)
-    for a, b in _chunks(lib, P, max_iterations):
-        n = b - a
-        ws = torch.empty(lib.xfh_relpose_workspace_bytes(n, int(max_iterations)) + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
-        ws.record_stream(stream)
-        tail = (_ptr(K0[a:b]), _ptr(K1[a:b]), float(max_epipolar_error), int(min_iterations), int(max_iterations), float(success_prob),
-                chunk_seed(seed, a), _ptr(R[a:b]), _ptr(t[a:b]), _ptr(E[a:b]), _ptr(mask[a:b]), _ptr(info[a:b]),
-                C.c_void_p(ws.data_ptr() + off), ws.numel() - off, C.c_void_p(stream.cuda_stream))
-        if index is None:
-            rc = lib.xfh_estimate_relpose(_ptr(pts0[a:b]), _ptr(pts1[a:b]), _ptr(counts[a:b]) if counts is not None else None, n_const, n, cap, *tail)
-        else:
-            idx0, idx1, kcap = index
-            rc = lib.xfh_estimate_relpose_matches(_ptr(pts0[a:b]), _ptr(pts1[a:b]), kcap, _ptr(idx0[a:b]), _ptr(idx1[a:b]), _ptr(counts[a:b]), n, cap, *tail)
-        _lib.check(rc, who)
+    fn = lib.xfh_estimate_relpose if index is None else lib.xfh_estimate_relpose_matches
+
+    def call(a, b, *ws_and_stream):
+        return fn(*_twoview.list_args(pts0, pts1, index, counts, n_const, a, b, cap), _ptr(K0[a:b]), _ptr(K1[a:b]), float(max_epipolar_error),
+                  int(min_iterations), int(max_iterations), float(success_prob), chunk_seed(seed, a), _ptr(R[a:b]), _ptr(t[a:b]), _ptr(E[a:b]),
+                  _ptr(mask[a:b]), _ptr(info[a:b]), *ws_and_stream)
+
+    _twoview.run_chunked(who, P, WORKSPACE_LIMIT, lambda n: lib.xfh_relpose_workspace_bytes(n, int(max_iterations)), dev, call)
     return out
 
 
@@ -100,17 +73,8 @@ def estimate_relative_pose_batch(pts0, pts1, counts, K0, K1, max_epipolar_error=
     max_epipolar_error is in pixels (Sampson error; converted with the mean focal length of the two cameras).
     Returns a dict of CUDA tensors: 'R' (P,3,3) float64, 't' (P,3) unit, 'E' (P,3,3) = [t]x R, 'inliers' (P,cap) uint8, 'info' (P,8) int32
     (INFO_FIELDS).  x1 in camera 0 maps to camera 1 as X1 = R X0 + t.  Asynchronous."""
-    dev = pts0.device if torch.is_tensor(pts0) and pts0.is_cuda else _device()
-    pts0 = torch.as_tensor(pts0).to(dev).float().contiguous()
-    pts1 = torch.as_tensor(pts1).to(dev).float().contiguous()
-    if pts0.dim() != 3 or pts0.shape[2] != 2 or pts1.shape != pts0.shape:
-        raise RuntimeError('expected two (P, cap, 2) point tensors of the same shape')
+    pts0, pts1, counts, dev = _twoview.check_points(_WHAT, pts0, pts1, counts)
     P, cap = pts0.shape[0], pts0.shape[1]
-    if counts is not None:
-        counts = torch.as_tensor(counts).to(dev).to(torch.int32).contiguous()
-        if counts.shape != (P,):
-            raise RuntimeError('counts must have one entry per pair')
-    K0, K1 = _intrinsics(K0, P, dev), _intrinsics(K1, P, dev)
     return _run("xfh_estimate_relpose", pts0, pts1, None, counts, cap, P, cap, K0, K1, max_epipolar_error, success_prob, min_iterations,
                 max_iterations, seed, dev)
 
@@ -120,16 +84,7 @@ def estimate_relative_pose_matches(kpts0, kpts1, idx0, idx1, n_matches, K0, K1, 
     """The same estimator straight on the matcher's output: correspondence i of pair p is (kpts0[p, idx0[p, i]], kpts1[p, idx1[p, i]])
     for i < n_matches[p].  kpts (P,K,2) float32, idx (P,cap) int64, n_matches (P,) int32 CUDA tensors, as ``XFeat._detect_device`` and
     ``XFeat.match_pairs_device`` return them.  Same result dict as estimate_relative_pose_batch."""
-    if not kpts0.is_cuda:
-        raise _lib.XFeatHipError("estimate_relative_pose_matches works on device-resident match lists")
-    dev = kpts0.device
-    P, cap = idx0.shape
-    if kpts0.shape != kpts1.shape or kpts0.shape[0] != P or kpts0.shape[2] != 2 or idx1.shape != idx0.shape or n_matches.shape != (P,):
-        raise RuntimeError('expected kpts (P,K,2), idx (P,cap), n_matches (P,)')
-    for t, dt in ((kpts0, torch.float32), (kpts1, torch.float32), (idx0, torch.int64), (idx1, torch.int64), (n_matches, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError('estimate_relative_pose_matches: contiguous float32 key-points, int64 indices, int32 counts expected')
-    K0, K1 = _intrinsics(K0, P, dev), _intrinsics(K1, P, dev)
+    dev, P, cap = _twoview.check_matches("estimate_relative_pose_matches", kpts0, kpts1, idx0, idx1, n_matches)
     return _run("xfh_estimate_relpose_matches", kpts0, kpts1, (idx0, idx1, kpts0.shape[1]), n_matches, 0, P, cap, K0, K1,
                 max_epipolar_error, success_prob, min_iterations, max_iterations, seed, dev)
 
@@ -158,14 +113,13 @@ def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, bund
     if bundle_opt not in (None, {}):
         raise _lib.XFeatHipError("estimate_relative_pose: bundle options are not supported (the evaluation passes {})")
     K0, K1 = _camera_K(camera0), _camera_K(camera1)
-    a = torch.as_tensor(np.asarray(kpts0) if not torch.is_tensor(kpts0) else kpts0).reshape(-1, 2)
-    b = torch.as_tensor(np.asarray(kpts1) if not torch.is_tensor(kpts1) else kpts1).reshape(-1, 2)
+    a, b = _twoview.as_points(kpts0), _twoview.as_points(kpts1)
     if a.shape != b.shape:
         raise RuntimeError('kpts0 and kpts1 must hold the same number of points')
     n = a.shape[0]
     if n < 5:
         return None, {"inliers": [False] * n, "num_inliers": 0, "iterations": 0, "refinements": 0}
-    dev = _device()
+    dev = _twoview.device(_WHAT)
     r = estimate_relative_pose_batch(a.to(dev).float()[None], b.to(dev).float()[None], None, K0, K1, opt["max_epipolar_error"],
                                      opt["success_prob"], opt["min_iterations"], opt["max_iterations"], seed)
     info = r['info'][0].cpu().tolist()
@@ -232,7 +186,7 @@ def pose_benchmark(xfeat, pairs, K0, K1, T_0to1, scale0=None, scale1=None, ransa
     for p in range(P):
         k = len(m0[p])
         pts0[p, :k], pts1[p, :k], counts[p] = m0[p].cpu(), m1[p].cpu(), k
-    r = estimate_relative_pose_batch(pts0.to(_device()), pts1.to(_device()), counts, np.asarray(K0)[:P], np.asarray(K1)[:P], ransac_thr,
+    r = estimate_relative_pose_batch(pts0, pts1, counts, np.asarray(K0)[:P], np.asarray(K1)[:P], ransac_thr,
                                      RANSAC_DEFAULTS["success_prob"], RANSAC_DEFAULTS["min_iterations"], RANSAC_DEFAULTS["max_iterations"], seed)
     info, R, t = r['info'].cpu().numpy(), r['R'].cpu().numpy(), r['t'].cpu().numpy()
     t_err, R_err = np.full(P, np.inf), np.full(P, np.inf)

@@ -1,5 +1,6 @@
 // fm_solve and fm_fit8 (csrc/k_fundamental.hip: the 7-point solver with the oriented constraint, the 8-point fit with its Jacobi sweeps;
-// sliced out of the product source by tests/test_fundamental_emulated.py into fundamental_slice.hpp) on the host, with the per-thread
+// sliced out of the product source, behind the shared geometry of csrc/twoview_math.hpp, by tests/test_fundamental_emulated.py into
+// fundamental_slice.hpp) on the host, with the per-thread
 // LDS slice as a plain array (stride 1).
 // stdin: mode int32, H int32, then
 //   mode 0 (solver): oriented int32, x0 y0 x1 y1 (H, 7) fp64 each, conditioning (H, 6) fp64; stdout: ncand (H) int32, candidates (H, 3, 9)
@@ -30,7 +31,7 @@ int main() {
                 for (int k = 0; k < 7; ++k) slice[xfh::FM_PTS + 7 * c + k] = in[(size_t)c * H * 7 + (size_t)h * 7 + k];
             const double* q = &nt[(size_t)h * 6];
             const xfh::FmNorm t{q[0], q[1], q[2], q[3], q[4], q[5]};
-            nc[h] = xfh::fm_solve(xfh::FmSlice<1>{slice}, t, oriented != 0, &out[(size_t)h * 27]);
+            nc[h] = xfh::fm_solve(xfh::tv::Slice<1>{slice}, t, oriented != 0, &out[(size_t)h * 27]);
         }
         fwrite(nc.data(), 4, H, stdout);
         fwrite(out.data(), 8, out.size(), stdout);

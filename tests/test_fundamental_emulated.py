@@ -1,6 +1,7 @@
-"""fm_solve and fm_fit8 (csrc/k_fundamental.hip) compiled for the HOST (tests/emu/fundamental_emu.cpp, fp contraction off) against the numpy
-restatement tests/fundamental_reference.py: on random, noise-free, noisy and near-degenerate samples the candidates must be equal bit for
-bit, and so must the 8-point fit; a negative control edits the slice and shows the comparison notices."""
+"""fm_solve and fm_fit8 (csrc/k_fundamental.hip, on the shared geometry of csrc/twoview_math.hpp) compiled for the HOST
+(tests/emu/fundamental_emu.cpp, fp contraction off) against the numpy restatement tests/fundamental_reference.py: on random, noise-free,
+noisy and near-degenerate samples the candidates must be equal bit for bit, and so must the 8-point fit; two negative controls edit the
+slice (the solver's part, the shared header's part) and show that the comparison notices."""
 import os
 import subprocess
 import tempfile
@@ -16,12 +17,21 @@ EMU = os.path.join(ROOT, "tests", "emu")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 
+def _between(name, begin, end):
+    """(whole text, text between the two markers) of a product source file."""
+    t = open(os.path.join(CSRC, name)).read()
+    a = t.index(begin)
+    return t, t[a:t.index(end, a)]
+
+
 def _slice():
-    t = open(os.path.join(CSRC, "k_fundamental.hip")).read()
-    a = t.index("// ---- fm solver begin")
-    s = t[a:t.index("// ---- fm solver end", a)]
-    assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
-    return s.replace("__device__ ", "")
+    """The shared geometry (twoview_math.hpp, which must be host-compilable as a whole file) in front of the solver's own slice."""
+    header, shared = _between("twoview_math.hpp", "// ---- twoview math begin", "// ---- twoview math end")
+    _, solver = _between("k_fundamental.hip", "// ---- fm solver begin", "// ---- fm solver end")
+    for s in (header, solver):
+        assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
+    assert "gauss_jordan" in shared and "gauss_jordan(S s" not in solver
+    return (shared + solver).replace("__device__ ", "")
 
 
 def _build(src):
@@ -156,6 +166,20 @@ def test_negative_control_an_edited_solver_is_caught():
     assert edited != src
     emu = _build(edited)
     rng = np.random.default_rng(11)
+    x, nt = _samples(rng, 400)
+    cand, nc = _run_solve(emu, x, nt)
+    want, wnc = FR.solve(*x, nt.T)
+    assert not np.array_equal(nc, wnc) or _compare(cand, nc, want, wnc) is not None
+
+
+def test_negative_control_an_edited_shared_header_is_caught():
+    """The same for the shared geometry: one differently rounded operation in twoview_math.hpp's Gauss-Jordan (the pivot row divided by
+    the pivot instead of multiplied by its reciprocal) must break the bit-for-bit comparison."""
+    src = _slice()
+    edited = src.replace("s[base + c * cols + j] = s[base + c * cols + j] * inv;", "s[base + c * cols + j] = s[base + c * cols + j] / (1.0 / inv);")
+    assert edited != src
+    emu = _build(edited)
+    rng = np.random.default_rng(12)
     x, nt = _samples(rng, 400)
     cand, nc = _run_solve(emu, x, nt)
     want, wnc = FR.solve(*x, nt.T)

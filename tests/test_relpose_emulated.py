@@ -1,5 +1,6 @@
-"""relpose_solve (csrc/k_relpose.hip) compiled for the HOST (tests/emu/relpose_emu.cpp, fp contraction off) against the numpy restatement
-tests/pose_reference.py: on random, noise-free, noisy and near-degenerate samples the candidate poses must be equal bit for bit."""
+"""relpose_solve (csrc/k_relpose.hip, on the shared geometry of csrc/twoview_math.hpp) compiled for the HOST (tests/emu/relpose_emu.cpp,
+fp contraction off) against the numpy restatement tests/pose_reference.py: on random, noise-free, noisy and near-degenerate samples the
+candidate poses must be equal bit for bit."""
 import os
 import subprocess
 import tempfile
@@ -15,12 +16,21 @@ EMU = os.path.join(ROOT, "tests", "emu")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 
+def _between(name, begin, end):
+    """(whole text, text between the two markers) of a product source file."""
+    t = open(os.path.join(CSRC, name)).read()
+    a = t.index(begin)
+    return t, t[a:t.index(end, a)]
+
+
 def _slice():
-    t = open(os.path.join(CSRC, "k_relpose.hip")).read()
-    a = t.index("// ---- solver begin")
-    s = t[a:t.index("// ---- solver end", a)]
-    assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
-    return s.replace("__device__ ", "")
+    """The shared geometry (twoview_math.hpp, which must be host-compilable as a whole file) in front of the solver's own slice."""
+    header, shared = _between("twoview_math.hpp", "// ---- twoview math begin", "// ---- twoview math end")
+    _, solver = _between("k_relpose.hip", "// ---- solver begin", "// ---- solver end")
+    for s in (header, solver):
+        assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
+    assert "gauss_jordan" in shared and "gauss_jordan(S s" not in solver
+    return (shared + solver).replace("__device__ ", "")
 
 
 @pytest.fixture(scope="module")
