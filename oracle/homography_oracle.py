@@ -31,19 +31,24 @@ The constants an implementation is free to choose (table size, MAX_THR_FACTOR, t
 the generator) are OURS, not OpenCV's: outputs are comparable with ``cv2.findHomography`` as estimates of the
 same homography (tests/test_oracle_homography.py pins the loss / weight formulas against numerical integration of
 the paper's marginalisation and the estimator against synthetic ground truth), not bit for bit.
+
+The generator, the table bin and integer quality, the loop's bound and the stopping-rule walk are the ones all three two-view
+restatements use (oracle/twoview_reference.py); this file keeps the MAGSAC++ integrals and tables, the four-point solver, the
+re-weighted DLT, and its evaluation of the whole hypothesis list at once.
 """
 import math
 
 import numpy as np
 from scipy import special
 
+from . import twoview_reference as TR
+from .twoview_reference import MAX_DRAWS, NBINS  # noqa: F401
+
 K_QUANTILE = 3.64            # 0.99 quantile of the chi distribution with 4 degrees of freedom (MAGSAC++ section 3)
 DOF = 4
 MAX_THR_FACTOR = 2.0         # residuals up to MAX_THR_FACTOR * threshold still carry weight
-NBINS = 4096                 # table bins over r^2 in [0, t_max^2)
 SCORE_ONE = 1 << 20          # fixed-point 1.0 of a table entry
 LO_ITERS = 5                 # re-weighted least-squares steps on the winner
-MAX_DRAWS = 16               # generator draws per sample before it is given up
 MASK64 = (1 << 64) - 1
 
 
@@ -93,35 +98,14 @@ def tables(thr):
 # --------------------------------------------------------------------------------------
 # sampling
 # --------------------------------------------------------------------------------------
-def _mix64(z):
-    z = z.astype(np.uint64)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    return z ^ (z >> np.uint64(31))
-
-
 def draw_index(seed, pair, it, draw, n):
-    """Draw ``draw`` of hypothesis ``it``: splitmix64 finaliser of a counter, upper 32 bits scaled to [0, n)."""
-    counter = (np.uint64(pair) * np.uint64(1 << 20) + np.asarray(it, np.uint64)) * np.uint64(MAX_DRAWS) + np.uint64(draw)
-    h = _mix64(np.uint64(seed & MASK64) + np.uint64(0x9e3779b97f4a7c15) * (counter + np.uint64(1)))
-    return (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+    """Draw ``draw`` of hypothesis ``it`` (the seed is taken modulo 2^64)."""
+    return TR.draw_index(seed & MASK64, pair, np.asarray(it, np.uint64), draw, n)
 
 
 def sample_sets(seed, pair, iters, n):
     """(idx (iters,4), ok (iters,)): four distinct indices per hypothesis, draws consumed in order, duplicates redrawn."""
-    it = np.arange(iters, dtype=np.uint64)
-    idx = np.full((iters, 4), -1, np.int64)
-    slot = np.zeros(iters, np.int64)
-    for d in range(MAX_DRAWS):
-        cand = draw_index(seed, pair, it, d, n)
-        dup = np.zeros(iters, bool)
-        for s in range(4):
-            dup |= (s < slot) & (idx[:, s] == cand)
-        take = (slot < 4) & ~dup
-        rows = np.nonzero(take)[0]
-        idx[rows, slot[rows]] = cand[rows]
-        slot[rows] += 1
-    return idx, slot == 4
+    return TR.sample_distinct(seed & MASK64, pair, np.arange(iters, dtype=np.uint64), n, 4)
 
 
 # --------------------------------------------------------------------------------------
@@ -193,24 +177,11 @@ def residuals_sq(h, p0, p1):
 def quality(r2, thr, bin_scale, score_table):
     """(integer MAGSAC++ score, inlier count at thr) per row of r2 (K,n)."""
     t_max = MAX_THR_FACTOR * thr
-    with np.errstate(invalid="ignore"):
-        near = r2 < t_max * t_max
-        b = np.where(near, r2 * bin_scale, 0.0).astype(np.int64)
-        b = np.minimum(b, NBINS - 1)
-        score = np.where(near, score_table[b].astype(np.int64), 0).sum(axis=1)
-        cnt = (r2 < thr * thr).sum(axis=1)
-    return score, cnt
+    return TR.quality(r2, thr * thr, t_max * t_max, bin_scale, score_table)
 
 
 def iterations_needed(inliers, n, confidence, max_iters):
-    w = inliers / n
-    p = 1.0 - w * w * w * w
-    if p <= 0.0:
-        return 1
-    if p >= 1.0:
-        return max_iters
-    k = math.log(1.0 - confidence) / math.log(p)
-    return int(min(float(max_iters), math.ceil(k)))
+    return TR.iterations_needed(inliers, n, math.log(1.0 - confidence), max_iters, 4)
 
 
 # --------------------------------------------------------------------------------------
@@ -273,13 +244,9 @@ def find_homography(points1, points2, ransac_thr, max_iters=700, confidence=0.99
         score += s
         cnt += c
     score[~valid] = 0
-    # the stopping rule, applied as the sequential loop applies it
-    best, best_s, k_stop, it = -1, 0, max_iters, 0
-    while it < max_iters and it < k_stop:
-        if score[it] > best_s:
-            best, best_s = it, int(score[it])
-            k_stop = min(k_stop, iterations_needed(int(cnt[it]), n, confidence, max_iters))
-        it += 1
+    # the stopping rule, applied as the sequential loop applies it: the whole list is one block of one-candidate hypotheses
+    whole = lambda its: (score[:, None], cnt[:, None], hyp[:, None], valid.astype(np.int64))      # noqa: E731
+    best, _, _, it = TR.stopping_rule(whole, n, math.log(1.0 - confidence), max_iters, 4, lower=False, block=max(max_iters, 1))
     info["iters"] = it
     if best < 0:
         return (None, None, info) if return_info else (None, None)
@@ -297,9 +264,7 @@ def find_homography(points1, points2, ransac_thr, max_iters=700, confidence=0.99
         info["lo_accepted"] = step
         if step == LO_ITERS:
             break
-        with np.errstate(invalid="ignore"):
-            near = r2[0] < t_max2
-            b = np.minimum(np.where(near, r2[0] * bin_scale, 0.0).astype(np.int64), NBINS - 1)
+        near, b = TR.table_bin(r2[0], t_max2, bin_scale)
         w = np.where(near, wtab[b], 0.0)
         h_new = weighted_dlt(p0, p1, w, norm0, norm1)
         if h_new is None or not np.all(np.isfinite(h_new)):

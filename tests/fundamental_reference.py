@@ -9,22 +9,27 @@ sums are formed in the select kernel's fixed block order and its Jacobi sweeps a
 The one function outside + - * / sqrt is the bound's log, as in the kernel.  The MAGSAC++ tables are the homography's: pass the ones
 the device computed (``xfh_homography_tables``) to compare with the kernels; by default they come from oracle/homography_oracle.py,
 whose quality table equals the device's and whose weights agree to 1e-12.
+
+Here is what only this estimator has: the cubic, the 7-point solver, Jacobi and the 8-point fit, the non-robust modes.  The draws, the
+stopping rule, the table lookups, the fixed-order sums, the Hartley conditioning and the geometry it shares with the other two
+restatements are oracle/twoview_reference.py's (the host side of csrc/ransac_common.hpp and csrc/twoview_math.hpp); ground truth and
+the synthetic scenes are tests/twoview_support.py's.
 """
 import math
 
 import numpy as np
 
-import pose_reference as PR
+from oracle import twoview_reference as TR
+from oracle.twoview_reference import MAX_DRAWS, NBINS, PIVOT_EPS, SQRT2, block_sums, cross, dot, finite, gauss_jordan, pmul, quality, sampson  # noqa: F401
+from oracle.twoview_reference import hartley_conditioning as conditioning  # noqa: F401  (the prep kernel's)
+from twoview_support import f_distance, sampson_px, true_F  # noqa: F401  (ground truth and test data, under the names the tests use)
 
-MAX_DRAWS, LO_ITERS, MAX_ITERS, MAX_CAND, NBINS = 16, 5, 16384, 3, 4096
+SAMPLE, LO_ITERS, MAX_ITERS, MAX_CAND = 7, 5, 16384, 3
 BISECT_STEPS, NEWTON_STEPS, JACOBI_SWEEPS = 64, 3, 10
-PIVOT_EPS = 1e-12
 FLT_EPS = 1.1920928955078125e-07
 FIT_RANK_EPS = 1e-12
 MAX_THR_FACTOR = 2.0
 FM_7POINT, FM_8POINT, USAC_MAGSAC = 1, 2, 38
-SQRT2 = 1.41421356237309504880
-GOLDEN = np.uint64(0x9e3779b97f4a7c15)
 
 
 def tables(thr):
@@ -38,21 +43,7 @@ def bin_scale_of(thr):
     return NBINS / (t_max * t_max)
 
 
-# ---- small helpers ---------------------------------------------------------------------------------------------------------------------------
-finite, cross, dot, pmul = PR.finite, PR.cross, PR.dot, PR.pmul
-
-
-def sampson(F, a, b, c, d):
-    e0 = (F[0] * a + F[1] * b) + F[2]
-    e1 = (F[3] * a + F[4] * b) + F[5]
-    e2 = (F[6] * a + F[7] * b) + F[8]
-    f0 = (F[0] * c + F[3] * d) + F[6]
-    f1 = (F[1] * c + F[4] * d) + F[7]
-    num = (c * e0 + d * e1) + e2
-    den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1
-    return num * num / den
-
-
+# ---- small helpers (the shared ones are oracle/twoview_reference.py's) ---------------------------------------------------------------------
 def cubic(a, x):
     return ((x + a[2]) * x + a[1]) * x + a[0]
 
@@ -129,7 +120,7 @@ def solve(x0, y0, x1, y1, nt, oriented=True):
             a, b, c, d = x0[:, k], y0[:, k], x1[:, k], y1[:, k]
             for j, v in enumerate((c * a, c * b, c, d * a, d * b, d, a, b, 1.0)):
                 A[:, k, j] = v
-        ok = PR.gauss_jordan(A)
+        ok = gauss_jordan(A)
         f2, D = [], []
         for m in range(9):
             v1 = -A[:, m, 7] if m < 7 else np.full(H, 1.0 if m == 7 else 0.0)
@@ -288,37 +279,7 @@ def scale_out(F):
 # ---- sampling, conditioning, the estimator ----------------------------------------------------------------------------------------------
 def draws(seed, pair, its, n):
     """Sample indices (H, 7) and ok (H,) of hypotheses `its` of pair `pair` with n correspondences."""
-    its = np.asarray(its, np.uint64)
-    H = its.shape[0]
-    idx = np.full((H, 7), -1, np.int64)
-    slot = np.zeros(H, np.int64)
-    with np.errstate(over="ignore"):
-        for d in range(MAX_DRAWS):
-            counter = (np.uint64(pair) * np.uint64(1 << 20) + its) * np.uint64(MAX_DRAWS) + np.uint64(d)
-            h = PR.mix64(np.uint64(seed) + GOLDEN * (counter + np.uint64(1)))
-            c = (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
-            dup = np.zeros(H, bool)
-            for k in range(6):
-                dup |= (slot > k) & (c == idx[:, k])
-            take = (slot < 7) & ~dup
-            for k in range(7):
-                idx[:, k] = np.where(take & (slot == k), c, idx[:, k])
-            slot += take
-    return idx, slot >= 7
-
-
-def conditioning(P0, P1):
-    """The prep kernel's Hartley similarities (cx0, cy0, s0, cx1, cy1, s1) of fp64 pixel arrays (n, 2)."""
-    n = P0.shape[0]
-    c = PR.block_sums(np.c_[P0, P1]) if n else np.zeros(4)
-    dn = float(max(n, 1))
-    cx0, cy0, cx1, cy1 = (float(v) / dn for v in c)
-    with np.errstate(all="ignore"):
-        ax, ay, bx, by = P0[:, 0] - cx0, P0[:, 1] - cy0, P1[:, 0] - cx1, P1[:, 1] - cy1
-        d = PR.block_sums(np.c_[np.sqrt(ax * ax + ay * ay), np.sqrt(bx * bx + by * by)]) if n else np.zeros(2)
-        s0 = SQRT2 / (float(d[0]) / dn) if d[0] > 0.0 else 1.0
-        s1 = SQRT2 / (float(d[1]) / dn) if d[1] > 0.0 else 1.0
-    return (cx0, cy0, s0, cx1, cy1, s1)
+    return TR.sample_distinct(seed, pair, its, n, SAMPLE)
 
 
 def normalised(P0, P1, nt):
@@ -327,24 +288,7 @@ def normalised(P0, P1, nt):
 
 
 def iterations_needed(inliers, n, log1mc, max_iters):
-    w = inliers / n
-    p = 1.0 - ((((((w * w) * w) * w) * w) * w) * w)
-    if p <= 0.0:
-        return 1
-    if p >= 1.0:
-        return max_iters
-    k = math.ceil(log1mc / math.log(p))
-    return k if k < max_iters else max_iters
-
-
-def quality(r2, thr2, tmax2, bin_scale, stab):
-    """(integer MAGSAC++ quality, inlier count) per row of r2 (..., n)."""
-    with np.errstate(invalid="ignore"):
-        near = r2 < tmax2
-        b = np.minimum(np.where(near, r2 * bin_scale, 0.0).astype(np.int64), NBINS - 1)
-        q = np.where(near, stab[b].astype(np.int64), 0).sum(axis=-1)
-        cnt = (r2 < thr2).sum(axis=-1)
-    return q, cnt
+    return TR.iterations_needed(inliers, n, log1mc, max_iters, SAMPLE)
 
 
 def hypotheses(P0, P1, nt, seed, pair, its, thr, tab):
@@ -379,8 +323,7 @@ def refine_terms(P0, P1, F, nt, thr, tab, robust=True):
     with np.errstate(all="ignore"):
         if robust:
             r2 = sampson(F, P0[:, 0], P0[:, 1], P1[:, 0], P1[:, 1])
-            near = r2 < tmax2
-            b = np.minimum(np.where(near, r2 * bin_scale, 0.0).astype(np.int64), NBINS - 1)
+            near, b = TR.table_bin(r2, tmax2, bin_scale)
             q = int(np.where(near, stab[b].astype(np.int64), 0).sum())
             w = wtab[b]
         else:
@@ -395,11 +338,6 @@ def refine_terms(P0, P1, F, nt, thr, tab, robust=True):
                 T[:, k] = np.where(near, wi * r[j], 0.0)
                 k += 1
     return q, T
-
-
-def _info_word(v):
-    v &= 0xffffffff
-    return v - (1 << 32) if v >= 1 << 31 else v
 
 
 def estimate(pts0, pts1, ransac_thr=3.0, max_iters=1000, confidence=0.99, seed=0, pair=0, method=USAC_MAGSAC, tab=None):
@@ -424,7 +362,7 @@ def estimate(pts0, pts1, ransac_thr=3.0, max_iters=1000, confidence=0.99, seed=0
         if n < 8:
             return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
         _, T = refine_terms(P0, P1, None, nt, thr, None, robust=False)
-        Fp = fit8(PR.block_sums(T), nt)
+        Fp = fit8(block_sums(T), nt)
         if Fp is None:
             return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
         out_F[0] = scale_out(Fp)
@@ -433,26 +371,9 @@ def estimate(pts0, pts1, ransac_thr=3.0, max_iters=1000, confidence=0.99, seed=0
         raise ValueError(f"method {method}")
     tab = tables(thr) if tab is None else tab
     log1mc = math.log(1.0 - confidence)
-    if n < 7:
+    if n < SAMPLE:
         return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
-    best, best_q, best_F, stop, it, h = -1, 0, None, max_iters, 0, 0
-    done = False
-    for base in range(0, max_iters, 256):
-        its = np.arange(base, min(base + 256, max_iters))
-        qs, cnts, cand, nc = hypotheses(P0, P1, nt, seed, pair, its, thr, tab)
-        for i, h in enumerate(its):
-            if h >= stop:
-                done = True
-                break
-            if nc[i] > 0:
-                c = int(np.argmax(qs[i, :nc[i]]))            # first maximum
-                if qs[i, c] > best_q:
-                    best, best_q, best_F = int(h), int(qs[i, c]), cand[i, c].copy()
-                    stop = min(stop, iterations_needed(int(cnts[i, c]), n, log1mc, max_iters))
-            it = int(h) + 1
-        if done:
-            it = int(h)
-            break
+    best, _, best_F, it = TR.stopping_rule(lambda its: hypotheses(P0, P1, nt, seed, pair, its, thr, tab), n, log1mc, max_iters, SAMPLE, lower=False)
     if best < 0:
         return dict(F=out_F, mask=zero_mask, info=np.array([0, -1, it, 0, 0, n, 0, 0]))
     Fc = [float(v) for v in best_F]
@@ -464,41 +385,18 @@ def estimate(pts0, pts1, ransac_thr=3.0, max_iters=1000, confidence=0.99, seed=0
         Fb, s_best, lo = Fc, s_now, step
         if step == LO_ITERS:
             break
-        up = fit8(PR.block_sums(T), nt)
+        up = fit8(block_sums(T), nt)
         if up is None:
             break
         Fc = up
     with np.errstate(all="ignore"):
         m = sampson(Fb, P0[:, 0], P0[:, 1], P1[:, 0], P1[:, 1]) < thr * thr
     n_in = int(m.sum())
-    found = n_in >= 7
-    info = np.array([int(found), best, it, n_in if found else 0, lo, n, _info_word(s_best), _info_word(s_best >> 32)])
+    found = n_in >= SAMPLE
+    info = np.array([int(found), best, it, n_in if found else 0, lo, n, *TR.info_words(s_best)])
     if found:
         out_F[0] = scale_out(Fb)
     return dict(F=out_F, mask=(m & found).astype(np.uint8), info=info)
-
-
-# ---- ground truth and test data ---------------------------------------------------------------------------------------------------------
-def true_F(K0, K1, T_0to1):
-    """F = K1^-T [t]x R K0^-1 of X1 = R X0 + t (unit Frobenius norm)."""
-    T = np.asarray(T_0to1, np.float64)
-    F = np.linalg.inv(np.asarray(K1, np.float64)).T @ PR.essential_from_pose(T[:3, :3], T[:3, 3]) @ np.linalg.inv(np.asarray(K0, np.float64))
-    return F / np.linalg.norm(F)
-
-
-def f_distance(F, G):
-    """Distance of two F up to scale and sign: min over the sign of |F/|F| -+ G/|G||_F."""
-    F = np.asarray(F, np.float64).reshape(3, 3)
-    G = np.asarray(G, np.float64).reshape(3, 3)
-    F, G = F / np.linalg.norm(F), G / np.linalg.norm(G)
-    return min(np.linalg.norm(F - G), np.linalg.norm(F + G))
-
-
-def sampson_px(F, p0, p1):
-    """Sampson errors (pixels, not squared) of correspondences p0, p1 (n, 2) under F (3, 3)."""
-    F = np.asarray(F, np.float64).reshape(-1)
-    p0, p1 = np.asarray(p0, np.float64), np.asarray(p1, np.float64)
-    return np.sqrt(sampson(F, p0[:, 0], p0[:, 1], p1[:, 0], p1[:, 1]))
 
 
 # median Sampson error (px) of 200 held-out noise-free true correspondences per pair under the estimated F, over the synthetic

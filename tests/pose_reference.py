@@ -6,15 +6,21 @@ rounded once, as in the kernel's file with fp contraction off), vectorised over 
 the candidate poses of a sample (``solve``), the integer costs, the winner, the iteration count, the mask and -- because the
 refinement's sums are formed in the select kernel's fixed block order -- the refined pose.  The one function outside + - * / sqrt is
 the bound's log, as in the kernel (one ulp there moves the bound only when the quotient is within an ulp of an integer).
+
+Here is what only this estimator has: the five-point solver, the MSAC cost, the Gauss-Newton refinement.  The draws, the stopping rule,
+the fixed-order sums and the geometry it shares with the other two restatements are oracle/twoview_reference.py's (the host side of
+csrc/ransac_common.hpp and csrc/twoview_math.hpp); the synthetic scenes are tests/twoview_support.py's.
 """
 import math
 
 import numpy as np
 
-MAX_DRAWS, LO_ITERS, MAX_ITERS, MAX_CAND = 16, 10, 16384, 10
+from oracle import twoview_reference as TR
+from oracle.twoview_reference import MAX_DRAWS, PIVOT_EPS, block_sums, cross, dot, finite, gauss_jordan, mix64, pmul, sampson  # noqa: F401
+from twoview_support import essential_from_pose, megadepth_synthetic, synthetic_pair  # noqa: F401  (test data, under the names the tests use)
+
+SAMPLE, LO_ITERS, MAX_ITERS, MAX_CAND = 5, 10, 16384, 10
 STURM_STEPS, SIGN_STEPS, NEWTON_STEPS = 48, 48, 4
-PIVOT_EPS = 1e-12
-GOLDEN = np.uint64(0x9e3779b97f4a7c15)
 
 # monomials: linear (x, y, z, 1); quadratic (x2, y2, z2, xy, xz, yz, x, y, z, 1); cubic in Nister's order
 CUBIC = [(3, 0, 0), (0, 3, 0), (2, 1, 0), (1, 2, 0), (2, 0, 1), (2, 0, 0), (0, 2, 1), (0, 2, 0), (1, 1, 1), (1, 1, 0),
@@ -27,19 +33,7 @@ QL = [[CUBIC.index(_add(a, b)) for b in LIN] for a in QUAD]
 SYM = [[0, 1, 2], [1, 3, 4], [2, 4, 5]]
 
 
-# ---- small helpers (arrays broadcast; the kernel's operation order) ----------------------------------------------------------------------
-def finite(v):
-    return (v - v) == 0.0
-
-
-def cross(a, b):
-    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-
-
-def dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
+# ---- small helpers (arrays broadcast; the kernel's operation order; the shared ones are oracle/twoview_reference.py's) ---------------------
 def pose_E(R, t):
     """[t]x R; R a list of 9 (row-major), t a list of 3."""
     E = [None] * 9
@@ -48,17 +42,6 @@ def pose_E(R, t):
         E[3 + j] = t[2] * R[j] - t[0] * R[6 + j]
         E[6 + j] = t[0] * R[3 + j] - t[1] * R[j]
     return E
-
-
-def sampson(E, a, b, c, d):
-    e0 = (E[0] * a + E[1] * b) + E[2]
-    e1 = (E[3] * a + E[4] * b) + E[5]
-    e2 = (E[6] * a + E[7] * b) + E[8]
-    f0 = (E[0] * c + E[3] * d) + E[6]
-    f1 = (E[1] * c + E[4] * d) + E[7]
-    num = (c * e0 + d * e1) + e2
-    den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1
-    return num * num / den
 
 
 def cost(r2, thr2):
@@ -72,40 +55,6 @@ def horner(a, x):
     for c in a[-2::-1]:
         v = v * x + c
     return v
-
-
-def pmul(a, b):
-    c = [0.0] * (len(a) + len(b) - 1)
-    for i in range(len(a)):
-        for j in range(len(b)):
-            c[i + j] = c[i + j] + a[i] * b[j]
-    return c
-
-
-def gauss_jordan(M):
-    """In place on (H, rows, cols), partial pivoting on the first `rows` columns.  Returns ok (H,)."""
-    H, rows, cols = M.shape
-    ok = np.ones(H, bool)
-    ar = np.arange(H)
-    for c in range(rows):
-        a = np.abs(M[:, c:, c])
-        first_nan = np.isnan(a[:, 0])
-        cmp = np.where(np.isnan(a), -np.inf, a)
-        p = np.where(first_nan, 0, np.argmax(cmp, axis=1)) + c
-        best = a[ar, p - c]
-        ok &= best >= PIVOT_EPS
-        rc, rp = M[ar, c].copy(), M[ar, p].copy()
-        M[ar, p] = rc
-        M[ar, c] = rp
-        inv = 1.0 / M[:, c, c]
-        M[:, c, c + 1:] = M[:, c, c + 1:] * inv[:, None]
-        M[:, c, c] = 1.0
-        f = M[:, :, c].copy()
-        upd = M[:, :, c + 1:] - f[:, :, None] * M[:, c:c + 1, c + 1:]
-        others = np.arange(rows) != c
-        M[:, others, c + 1:] = upd[:, others]
-        M[:, others, c] = 0.0
-    return ok
 
 
 # ---- the minimal solver -------------------------------------------------------------------------------------------------------------------
@@ -304,31 +253,9 @@ def solve(x1, y1, x2, y2):
 
 
 # ---- sampling, calibration, the estimator -----------------------------------------------------------------------------------------------
-def mix64(z):
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    return z ^ (z >> np.uint64(31))
-
-
 def draws(seed, pair, its, n):
     """Sample indices (H, 5) and ok (H,) of hypotheses `its` of pair `pair` with n correspondences."""
-    its = np.asarray(its, np.uint64)
-    H = its.shape[0]
-    idx = np.full((H, 5), -1, np.int64)
-    slot = np.zeros(H, np.int64)
-    with np.errstate(over="ignore"):
-        for d in range(MAX_DRAWS):
-            counter = (np.uint64(pair) * np.uint64(1 << 20) + its) * np.uint64(MAX_DRAWS) + np.uint64(d)
-            h = mix64(np.uint64(seed) + GOLDEN * (counter + np.uint64(1)))
-            c = (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
-            dup = np.zeros(H, bool)
-            for k in range(4):
-                dup |= (slot > k) & (c == idx[:, k])
-            take = (slot < 5) & ~dup
-            for k in range(5):
-                idx[:, k] = np.where(take & (slot == k), c, idx[:, k])
-            slot += take
-    return idx, slot >= 5
+    return TR.sample_distinct(seed, pair, its, n, SAMPLE)
 
 
 def calibrate(pts0, pts1, K0, K1):
@@ -348,14 +275,7 @@ def threshold2(max_err, K0, K1):
 
 
 def iterations_needed(inliers, n, log1mp, max_iters):
-    w = inliers / n
-    p = 1.0 - ((((w * w) * w) * w) * w)
-    if p <= 0.0:
-        return 1
-    if p >= 1.0:
-        return max_iters
-    k = math.ceil(log1mp / math.log(p))
-    return k if k < max_iters else max_iters
+    return TR.iterations_needed(inliers, n, log1mp, max_iters, SAMPLE)
 
 
 def hypotheses(X, seed, pair, its, thr2):
@@ -381,25 +301,6 @@ def hypotheses(X, seed, pair, its, thr2):
             costs[sel, c] = cost(r2, thr2).sum(axis=1)
             cnts[sel, c] = (r2 < thr2).sum(axis=1)
     return costs, cnts, cand, nc
-
-
-def block_sums(C):
-    """The select kernel's fixed-order totals of per-correspondence terms C (n, K): thread i % 256 in index order, 8 segments of 32 threads, a tree."""
-    n, K = C.shape
-    R = -(-n // 256)
-    Cp = np.zeros((max(R, 1) * 256, K))
-    Cp[:n] = C
-    acc = np.zeros((256, K))
-    for r in range(R):
-        acc = acc + Cp[r * 256:(r + 1) * 256]
-    part = np.zeros((8, K))
-    for j in range(8):
-        s = np.zeros(K)
-        for i in range(32):
-            s = s + acc[32 * j + i]
-        part[j] = s
-    q = part
-    return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]))
 
 
 def tangent(t):
@@ -471,14 +372,8 @@ def refine_terms(X, R, t, b1, b2, thr2):
     pa, pb, pc, pd = X
     with np.errstate(all="ignore"):
         E = pose_E(R, t)
-        e0 = (E[0] * pa + E[1] * pb) + E[2]
-        e1 = (E[3] * pa + E[4] * pb) + E[5]
-        e2 = (E[6] * pa + E[7] * pb) + E[8]
-        f0 = (E[0] * pc + E[3] * pd) + E[6]
-        f1 = (E[1] * pc + E[4] * pd) + E[7]
+        num, den, (f0, f1) = TR.sampson_terms(E, pa, pb, pc, pd)
         f2 = (E[2] * pc + E[5] * pd) + E[8]
-        num = (pc * e0 + pd * e1) + e2
-        den = ((e0 * e0 + e1 * e1) + f0 * f0) + f1 * f1
         r2 = num * num / den
         inl = r2 < thr2
         w = 1.0 / den
@@ -506,26 +401,10 @@ def estimate(pts0, pts1, K0, K1, max_epipolar_error=1.0, success_prob=0.99999, m
     thr2 = threshold2(max_epipolar_error, K0, K1)
     log1mp = math.log(1.0 - success_prob)
     zero = dict(R=np.zeros((3, 3)), t=np.zeros(3), E=np.zeros((3, 3)), mask=np.zeros(n, np.uint8))
-    if n < 5:
+    if n < SAMPLE:
         return dict(zero, info=np.array([0, -1, 0, 0, 0, n, 0, 0]))
-    best, best_cost, best_pose, stop, it = -1, None, None, max_iterations, 0
-    done = False
-    for base in range(0, max_iterations, 256):
-        its = np.arange(base, min(base + 256, max_iterations))
-        costs, cnts, cand, nc = hypotheses(X, seed, pair, its, thr2)
-        for i, h in enumerate(its):
-            if h >= max(stop, min_iterations):
-                done = True
-                break
-            if nc[i] > 0:
-                c = int(np.argmin(costs[i, :nc[i]]))          # first minimum
-                if best_cost is None or costs[i, c] < best_cost:
-                    best, best_cost, best_pose = int(h), int(costs[i, c]), cand[i, c].copy()
-                    stop = min(stop, iterations_needed(int(cnts[i, c]), n, log1mp, max_iterations))
-            it = int(h) + 1
-        if done:
-            it = int(h)
-            break
+    best, _, best_pose, it = TR.stopping_rule(lambda its: hypotheses(X, seed, pair, its, thr2), n, log1mp, max_iterations, SAMPLE, lower=True,
+                                              min_iters=min_iterations)
     if best < 0:
         return dict(zero, info=np.array([0, -1, it, 0, 0, n, 0, 0]))
     Rc, tc = [float(v) for v in best_pose[:9]], [float(v) for v in best_pose[9:]]
@@ -550,68 +429,14 @@ def estimate(pts0, pts1, K0, K1, max_epipolar_error=1.0, success_prob=0.99999, m
         Eb = pose_E(Rb, tb)
         m = sampson(Eb, *X) < thr2
     n_in = int(m.sum())
-    found = n_in >= 5
-    info = np.array([int(found), best, it, n_in, lo, n, c_best & 0xffffffff, c_best >> 32])
-    info[6] = info[6] - (1 << 32) if info[6] >= 1 << 31 else info[6]
+    found = n_in >= SAMPLE
+    info = np.array([int(found), best, it, n_in, lo, n, *TR.info_words(c_best)])
     if not found:
         return dict(zero, info=info)
     return dict(R=np.array(Rb).reshape(3, 3), t=np.array(tb), E=np.array(Eb).reshape(3, 3), mask=m.astype(np.uint8), info=info)
-
-
-# ---- evaluation helpers (the same definitions as accelerated_features_amd.pose, restated) ---------------------------------------------
-def essential_from_pose(R, t):
-    t = np.asarray(t, np.float64)
-    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
-    return tx @ np.asarray(R, np.float64)
-
-
-# ---- synthetic scenes (test data) --------------------------------------------------------------------------------------------------------
-def synthetic_pair(K0, K1, T_0to1, n, noise=0.5, outliers=0.0, size0=(480, 640), size1=(480, 640), rng=None):
-    """n correspondences (fp32 pixels) of 3D points in front of both cameras, seen in both images, with Gaussian pixel noise in image 1
-    and a fraction of outliers (uniform in image 1).  Returns pts0, pts1 (n, 2) float32 and the outlier flags."""
-    rng = np.random.default_rng(0) if rng is None else rng
-    K0, K1, T = (np.asarray(v, np.float64) for v in (K0, K1, T_0to1))
-    R, t = T[:3, :3], T[:3, 3]
-    h0, w0 = size0
-    h1, w1 = size1
-    depth = max(1.0, 4.0 * np.linalg.norm(t))
-    p0s, p1s = [], []
-    for rnd in range(1000):
-        if sum(len(p) for p in p0s) >= n:
-            break
-        m = 4 * n
-        uv = np.c_[rng.uniform(0, w0, m), rng.uniform(0, h0, m)]
-        z = rng.uniform(0.5 * depth, 2.0 * depth, m)
-        X = np.c_[(uv[:, 0] - K0[0, 2]) / K0[0, 0] * z, (uv[:, 1] - K0[1, 2]) / K0[1, 1] * z, z]
-        X1 = X @ R.T + t
-        ok = X1[:, 2] > 1e-3
-        u1 = K1[0, 0] * X1[:, 0] / np.where(ok, X1[:, 2], 1.0) + K1[0, 2]
-        v1 = K1[1, 1] * X1[:, 1] / np.where(ok, X1[:, 2], 1.0) + K1[1, 2]
-        if rnd < 20:                              # in image 1 as well; after 20 rounds (poses whose views barely overlap) in front of it only
-            ok &= (u1 >= 0) & (u1 < w1) & (v1 >= 0) & (v1 < h1)
-        p0s.append(uv[ok])
-        p1s.append(np.c_[u1, v1][ok])
-    p0 = np.concatenate(p0s)[:n]
-    p1 = np.concatenate(p1s)[:n] + rng.normal(size=(n, 2)) * noise
-    out = rng.random(n) < outliers
-    p1[out] = np.c_[rng.uniform(0, w1, out.sum()), rng.uniform(0, h1, out.sum())]
-    return p0.astype(np.float32), p1.astype(np.float32), out
 
 
 # AUC@5/10/20 floors of the synthetic MegaDepth-1500 set at max_epipolar_error 1 px, 1000 iterations, seed 0.  This restatement reaches
 # 0.975 / 0.987 / 0.994 on every 10th pair (test_pose_reference.py::test_megadepth_synthetic_auc_on_every_10th_pair computes it); the floors
 # leave a margin for the pairs it does not run.  test_gpu_relpose.py holds the kernels' AUC over all 1500 pairs to them.
 AUC_FLOORS = {"auc@5": 0.90, "auc@10": 0.94, "auc@20": 0.96}
-
-
-def megadepth_synthetic(f, P=1500, cap=1024, seed=1500):
-    """The synthetic MegaDepth-1500 set of the AUC tests: pair p on the fixture's K0 / K1 / T_0to1 / sizes, 200..cap correspondences,
-    0.5-1 px noise, 40 % outliers.  Returns pts0, pts1 (P, cap, 2) float32 and counts (P,) int32."""
-    rng = np.random.default_rng(seed)
-    pts0, pts1 = np.zeros((P, cap, 2), np.float32), np.zeros((P, cap, 2), np.float32)
-    counts = rng.integers(200, cap + 1, P).astype(np.int32)
-    for p in range(P):
-        a, b, _ = synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], int(counts[p]), rng.uniform(0.5, 1.0), 0.4, tuple(f["size0_hw"][p]),
-                                 tuple(f["size1_hw"][p]), rng)
-        pts0[p, :counts[p]], pts1[p, :counts[p]] = a, b
-    return pts0, pts1, counts

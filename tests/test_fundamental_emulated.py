@@ -2,47 +2,21 @@
 (tests/emu/fundamental_emu.cpp, fp contraction off) against the numpy restatement tests/fundamental_reference.py: on random, noise-free,
 noisy and near-degenerate samples the candidates must be equal bit for bit, and so must the 8-point fit; two negative controls edit the
 slice (the solver's part, the shared header's part) and show that the comparison notices."""
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import fundamental_reference as FR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "accelerated_features_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-
-
-def _between(name, begin, end):
-    """(whole text, text between the two markers) of a product source file."""
-    t = open(os.path.join(CSRC, name)).read()
-    a = t.index(begin)
-    return t, t[a:t.index(end, a)]
+import twoview_support as TS
 
 
 def _slice():
-    """The shared geometry (twoview_math.hpp, which must be host-compilable as a whole file) in front of the solver's own slice."""
-    header, shared = _between("twoview_math.hpp", "// ---- twoview math begin", "// ---- twoview math end")
-    _, solver = _between("k_fundamental.hip", "// ---- fm solver begin", "// ---- fm solver end")
-    for s in (header, solver):
-        assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
-    assert "gauss_jordan" in shared and "gauss_jordan(S s" not in solver
-    return (shared + solver).replace("__device__ ", "")
+    return TS.slice_solver("k_fundamental.hip", "// ---- fm solver begin", "// ---- fm solver end")
 
 
 def _build(src):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang")
-    td = tempfile.mkdtemp()
-    open(os.path.join(td, "fundamental_slice.hpp"), "w").write(src)
-    out = os.path.join(td, "fundamental_emu")
-    subprocess.run([CLANG, "-O2", "-w", "-std=c++20", "-ffp-contract=off", "-I", td, "-I", EMU, os.path.join(EMU, "fundamental_emu.cpp"), "-o",
-                    out], check=True)
-    return out
+    return TS.build_emu("fundamental_slice.hpp", "fundamental_emu", src)
 
 
 @pytest.fixture(scope="module")
@@ -66,35 +40,19 @@ def _run_fit(emu_bin, sums, nt):
     return np.frombuffer(out[:4 * H], np.int32), np.frombuffer(out[4 * H:], np.float64).reshape(H, 9)
 
 
-def _rotation(rng, scale):
-    w = rng.normal(size=3) * scale
-    th = np.linalg.norm(w)
-    k = w / th
-    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+def _degenerate(X, sub):
+    if sub == 0:
+        X[:, 2] = 4.0 + 0.1 * X[:, 0]                   # coplanar
+    elif sub == 1:
+        X[:, 1] = 0.3 * X[:, 2]                         # all on one plane through the first centre: collinear in image 0
+    else:
+        X[6] = X[5] * (1 + 1e-9)                         # a repeated point
 
 
 def _samples(rng, H):
     """7-point samples in normalised coordinates, four kinds: uniform noise, noise-free scenes, noisy scenes, near-degenerate (coplanar,
     collinear in one image, a repeated point); and a random conditioning per sample."""
-    x = rng.uniform(-1.5, 1.5, (4, H, 7))
-    kind = np.arange(H) % 4
-    for h in np.nonzero(kind > 0)[0]:
-        R, t = _rotation(rng, 0.3), rng.normal(size=3)
-        X = np.c_[rng.uniform(-1, 1, (7, 2)), rng.uniform(2, 6, 7)]
-        if kind[h] == 3:
-            sub = h % 3
-            if sub == 0:
-                X[:, 2] = 4.0 + 0.1 * X[:, 0]                   # coplanar
-            elif sub == 1:
-                X[:, 1] = 0.3 * X[:, 2]                         # all on one plane through the first centre: collinear in image 0
-            else:
-                X[6] = X[5] * (1 + 1e-9)                         # a repeated point
-        X2 = X @ R.T + t
-        x[0, h], x[1, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2]
-        x[2, h], x[3, h] = X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
-        if kind[h] == 2:
-            x[:, h] += rng.normal(size=(4, 7)) * 1e-3
+    x = TS.mixed_samples(rng, H, 7, 1.5, _degenerate)
     nt = np.c_[rng.uniform(100, 900, (H, 2)), rng.uniform(1e-3, 1e-2, H), rng.uniform(100, 900, (H, 2)), rng.uniform(1e-3, 1e-2, H)]
     return x, nt
 
@@ -140,7 +98,7 @@ def test_host_fit8_equals_the_restatement_bit_for_bit(emu_bin):
     H = 300
     sums, nts = np.zeros((H, 45)), np.zeros((H, 6))
     for h in range(H):
-        R, t = _rotation(rng, 0.4), rng.normal(size=3)
+        R, t = TS.rotation(rng.normal(size=3) * 0.4), rng.normal(size=3)
         n = int(rng.integers(8, 200))
         X = np.c_[rng.uniform(-1, 1, (n, 2)), rng.uniform(2, 6, n)]
         X2 = X @ R.T + t
@@ -149,7 +107,7 @@ def test_host_fit8_equals_the_restatement_bit_for_bit(emu_bin):
         w = rng.uniform(0, 1, n) if h % 3 else np.ones(n)
         r = [x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, np.ones(n)]
         T = np.stack([(w * r[i]) * r[j] for i in range(9) for j in range(i, 9)], axis=1)
-        sums[h] = FR.PR.block_sums(T)
+        sums[h] = FR.block_sums(T)
         nts[h] = [rng.uniform(0, 900), rng.uniform(0, 900), rng.uniform(1e-3, 1e-2), rng.uniform(0, 900), rng.uniform(0, 900), rng.uniform(1e-3, 1e-2)]
     ok, F = _run_fit(emu_bin, sums, nts)
     for h in range(H):

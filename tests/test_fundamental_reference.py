@@ -1,38 +1,18 @@
 """The fundamental-matrix restatement (tests/fundamental_reference.py) against ground truth, and the public surface of
 accelerated_features_amd.fundamental without a GPU.  CPU only: the restatement is what the GPU tests hold the kernels to, so it is checked
 here on its own."""
-import os
-
 import numpy as np
 import pytest
 
 import fundamental_reference as FR
 import pose_reference as PR
+from twoview_support import fixture as _fixture, fixture_pair, holdout, true_samples
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-POSES = os.path.join(HERE, "golden", "megadepth1500_poses.npz")
 IDENT = (0.0, 0.0, 1.0, 0.0, 0.0, 1.0)
 
 
-def _fixture():
-    return dict(np.load(POSES))
-
-
-def _rot(w):
-    th = np.linalg.norm(w)
-    k = w / th
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-
-
 def _samples(rng, H):
-    x = np.zeros((4, H, 7))
-    for h in range(H):
-        R, t = _rot(rng.normal(size=3) * 0.3), rng.normal(size=3)
-        X = np.c_[rng.uniform(-1, 1, (7, 2)), rng.uniform(2, 6, 7)]
-        X2 = X @ R.T + t
-        x[0, h], x[1, h], x[2, h], x[3, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2], X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
-    return x
+    return true_samples(rng, H, 7)[0]
 
 
 def test_every_candidate_is_a_rank_two_matrix_through_the_sample():
@@ -67,13 +47,11 @@ def test_true_F_is_among_the_candidates_on_the_megadepth_cameras():
     hits, dmin = 0, []
     P = 1500
     for p in range(0, P, 3):
-        p0, p1, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 7, 0.0, 0.0, tuple(f["size0_hw"][p]), tuple(f["size1_hw"][p]),
-                                      rng)
+        p0, p1, _ = fixture_pair(f, p, 7, 0.0, 0.0, rng)
         P0, P1 = p0.astype(np.float64), p1.astype(np.float64)
         nt = FR.conditioning(P0, P1)
         cand, nc = FR.solve(*FR.normalised(P0[None], P1[None], nt), nt)
-        h0, h1, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 100, 0.0, 0.0, tuple(f["size0_hw"][p]), tuple(f["size1_hw"][p]),
-                                      np.random.default_rng(p))
+        h0, h1 = holdout(f, p, 100)
         d = min([np.median(FR.sampson_px(cand[0, c], h0, h1)) for c in range(nc[0])] or [np.inf])
         dmin.append(d)
         hits += d <= 1e-2
@@ -118,12 +96,10 @@ def test_estimator_recovers_the_true_F_and_the_inliers(outliers, iters):
     i = 17
     rng = np.random.default_rng(int(outliers * 10))
     n = 400
-    p0, p1, out = PR.synthetic_pair(f["K0"][i], f["K1"][i], f["T_0to1"][i], n, 0.3, outliers, tuple(f["size0_hw"][i]), tuple(f["size1_hw"][i]),
-                                    rng)
+    p0, p1, out = fixture_pair(f, i, n, 0.3, outliers, rng)
     r = FR.estimate(p0, p1, 1.0, iters, 0.999, seed=3)
     assert r["info"][0] == 1
-    h0, h1, _ = PR.synthetic_pair(f["K0"][i], f["K1"][i], f["T_0to1"][i], 200, 0.0, 0.0, tuple(f["size0_hw"][i]), tuple(f["size1_hw"][i]),
-                                  np.random.default_rng(5))
+    h0, h1, _ = fixture_pair(f, i, 200, 0.0, 0.0, np.random.default_rng(5))
     e = FR.sampson_px(r["F"][0], h0, h1)
     assert np.median(e) <= 0.15 and np.percentile(e, 95) <= 0.5, (np.median(e), e.max())
     m = r["mask"].astype(bool)
@@ -136,7 +112,7 @@ def test_eight_point_equals_the_textbook_svd_fit():
     f = _fixture()
     for i in (3, 99, 1234):
         rng = np.random.default_rng(i)
-        p0, p1, _ = PR.synthetic_pair(f["K0"][i], f["K1"][i], f["T_0to1"][i], 60, 0.0, 0.0, tuple(f["size0_hw"][i]), tuple(f["size1_hw"][i]), rng)
+        p0, p1, _ = fixture_pair(f, i, 60, 0.0, 0.0, rng)
         r = FR.estimate(p0, p1, method=FR.FM_8POINT)
         assert list(r["info"]) == [1, -1, 1, 60, 0, 60, 0, 0] and r["mask"].all()
         P0, P1 = p0.astype(np.float64), p1.astype(np.float64)
@@ -180,8 +156,7 @@ def test_megadepth_synthetic_holdout_error_on_every_25th_pair():
         r = FR.estimate(pts0[p, :counts[p]], pts1[p, :counts[p]], 1.5, 1000, 0.99, seed=0, pair=p)
         found.append(r["info"][0])
         if r["info"][0]:
-            h0, h1, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 200, 0.0, 0.0, tuple(f["size0_hw"][p]),
-                                          tuple(f["size1_hw"][p]), np.random.default_rng(p))
+            h0, h1 = holdout(f, p, 200)
             med.append(np.median(FR.sampson_px(r["F"][0].reshape(3, 3), h0, h1)))
         else:
             med.append(np.inf)

@@ -2,7 +2,6 @@
 the iteration count, the inlier count, the integer quality and the mask exactly; F to 1e-9.  The restatement is given the tables the
 device computed (xfh_homography_tables), so the quality sums are the same integers."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -10,11 +9,9 @@ import torch
 
 import fundamental_reference as FR
 import pose_reference as PR
+from twoview_support import check_common, fixture as _fixture, holdout, scene
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-POSES = os.path.join(HERE, "golden", "megadepth1500_poses.npz")
 
 
 @pytest.fixture(scope="module")
@@ -40,23 +37,8 @@ def _tab(thr):
     return _TABLES[thr]
 
 
-def _fixture():
-    return dict(np.load(POSES))
-
-
-def _scene(i, n, noise, outliers, seed):
-    f = _fixture()
-    rng = np.random.default_rng(seed)
-    p0, p1, out = PR.synthetic_pair(f["K0"][i], f["K1"][i], f["T_0to1"][i], n, noise, outliers, tuple(f["size0_hw"][i]),
-                                    tuple(f["size1_hw"][i]), rng)
-    return p0, p1, out, FR.true_F(f["K0"][i], f["K1"][i], f["T_0to1"][i])
-
-
 def _check(got, want, p, n, method=FR.USAC_MAGSAC):
-    info = got["info"][p].cpu().numpy()
-    assert list(info) == list(want["info"]), (list(info), list(want["info"]))
-    assert np.array_equal(got["inliers"][p, :n].cpu().numpy(), want["mask"])
-    assert not got["inliers"][p, n:].any()
+    check_common(got, want, p, n)
     g = got["F"][p].cpu().numpy().reshape(-1, 9)
     w = want["F"] if method == FR.FM_7POINT else want["F"][:1]
     assert np.isfinite(g).all()
@@ -70,7 +52,7 @@ def _batch(fm, p0, p1, thr, iters, seed, counts=None, method=38, conf=0.99):
 @pytest.mark.parametrize("n,outliers,thr,iters", [(7, 0.0, 1.0, 1000), (8, 0.0, 3.0, 1000), (300, 0.3, 1.0, 1000), (300, 0.7, 3.0, 10000),
                                                   (2000, 0.5, 1.0, 1000), (4096, 0.6, 2.0, 4000), (2000, 0.0, 1.0, 16384)])
 def test_single_pair_equals_the_restatement(fm, n, outliers, thr, iters):
-    p0, p1, _, _ = _scene(7, n, 0.7, outliers, seed=n)
+    p0, p1 = scene(7, n, 0.7, outliers, seed=n)[:2]
     got = _batch(fm, p0[None], p1[None], thr, iters, 11)
     torch.cuda.synchronize()
     want = FR.estimate(p0, p1, thr, iters, 0.99, seed=11, tab=_tab(thr))
@@ -84,7 +66,7 @@ def test_ragged_batch_equals_the_restatement_pair_by_pair(fm):
     P, cap = len(ns), max(ns)
     pts0, pts1 = np.zeros((P, cap, 2), np.float32), np.zeros((P, cap, 2), np.float32)
     for p, n in enumerate(ns):
-        a, b, _, _ = _scene(100 + p, max(n, 1), 0.5, 0.4, seed=p)
+        a, b = scene(100 + p, max(n, 1), 0.5, 0.4, seed=p)[:2]
         pts0[p, :n], pts1[p, :n] = a[:n], b[:n]
     pts0[:, cap - 1] = np.nan                          # rows past the counts are never read
     got = _batch(fm, pts0, pts1, 1.5, 1000, 5, torch.tensor(ns, dtype=torch.int32))
@@ -99,7 +81,7 @@ def test_chunked_batch_equals_one_call(fm, monkeypatch):
     P, n = 5, 400
     pts0, pts1 = np.zeros((P, n, 2), np.float32), np.zeros((P, n, 2), np.float32)
     for p in range(P):
-        pts0[p], pts1[p], _, _ = _scene(200 + p, n, 0.6, 0.5, seed=p)
+        pts0[p], pts1[p] = scene(200 + p, n, 0.6, 0.5, seed=p)[:2]
     one = _batch(fm, pts0, pts1, 2.0, 1000, 3)
     monkeypatch.setattr(fm, "WORKSPACE_LIMIT", 2 * fm._lib.load().xfh_fundamental_workspace_bytes(1, 1000))
     many = _batch(fm, pts0, pts1, 2.0, 1000, 3)
@@ -115,7 +97,7 @@ def test_index_list_entry_equals_gathered_points(fm):
     idx0, idx1 = np.zeros((P, cap), np.int64), np.zeros((P, cap), np.int64)
     nm = np.array([500, 333, 20], np.int32)
     for p in range(P):
-        a, b, _, _ = _scene(p, K, 0.5, 0.3, seed=p)
+        a, b = scene(p, K, 0.5, 0.3, seed=p)[:2]
         kp0[p], kp1[p] = a, b[rng.permutation(K)]
         idx0[p] = rng.choice(K, cap, replace=False)
         idx1[p] = rng.choice(K, cap, replace=False)
@@ -131,7 +113,7 @@ def test_index_list_entry_equals_gathered_points(fm):
 
 
 def test_same_seed_same_bits(fm):
-    p0, p1, _, _ = _scene(3, 1500, 1.0, 0.5, seed=1)
+    p0, p1 = scene(3, 1500, 1.0, 0.5, seed=1)[:2]
     a = _batch(fm, p0[None], p1[None], 1.0, 1000, 4)
     b = _batch(fm, p0[None], p1[None], 1.0, 1000, 4)
     torch.cuda.synchronize()
@@ -173,7 +155,7 @@ def test_seven_and_eight_point_modes_equal_the_restatement(fm):
     rng = np.random.default_rng(8)
     pts0, pts1 = np.zeros((P, 40, 2), np.float32), np.zeros((P, 40, 2), np.float32)
     for p in range(P):
-        pts0[p], pts1[p], _, _ = _scene(300 + p, 40, 0.3 * (p % 2), 0.0, seed=p)
+        pts0[p], pts1[p] = scene(300 + p, 40, 0.3 * (p % 2), 0.0, seed=p)[:2]
     ns = np.array([7, 7, 7, 40, 8, 6], np.int32)
     r7 = _batch(fm, pts0, pts1, 1.0, 1, 0, torch.from_numpy(ns), 1)
     r8 = _batch(fm, pts0, pts1, 1.0, 1, 0, torch.from_numpy(ns), 2)
@@ -197,8 +179,7 @@ def test_megadepth1500_holdout_error(fm):
     med = np.full(P, np.inf)
     for p in range(P):
         if info[p, 0]:
-            h0, h1, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 200, 0.0, 0.0, tuple(f["size0_hw"][p]),
-                                          tuple(f["size1_hw"][p]), np.random.default_rng(p))
+            h0, h1 = holdout(f, p, 200)
             med[p] = np.median(FR.sampson_px(F[p], h0, h1))
     found = info[:, 0].mean()
     print("synthetic MegaDepth-1500: found", found, "median", np.median(med), "p90", np.percentile(med, 90))
@@ -211,7 +192,7 @@ def test_megadepth1500_holdout_error(fm):
 
 
 def test_cv2_shaped_wrapper_equals_the_batch_entry(fm):
-    p0, p1, _, _ = _scene(11, 800, 0.5, 0.3, seed=2)
+    p0, p1 = scene(11, 800, 0.5, 0.3, seed=2)[:2]
     F, mask = fm.find_fundamental_mat(p0, p1, fm.USAC_MAGSAC, 1.5, 0.999, 2000)
     r = _batch(fm, p0[None], p1[None], 1.5, 2000, 0, conf=0.999)
     assert np.array_equal(F, r["F"][0].cpu().numpy()) and F.shape == (3, 3) and F[2, 2] == 1.0

@@ -11,7 +11,8 @@ import torch
 
 import fixtures
 from oracle import homography_oracle as ho
-from test_oracle_homography import synthetic_pair, transfer_error
+from test_oracle_homography import transfer_error
+from twoview_support import homography_pair as synthetic_pair
 
 pytestmark = pytest.mark.gpu
 

@@ -1,17 +1,13 @@
 """xfh_estimate_relpose (csrc/k_relpose.hip) on the MI355X against the numpy restatement tests/pose_reference.py: the winner, the
 iteration count, the inlier count, the integer cost and the mask exactly; R, t and E to 1e-9."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import pose_reference as PR
+from twoview_support import check_common, fixture as _fixture, scene
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-POSES = os.path.join(HERE, "golden", "megadepth1500_poses.npz")
 
 
 @pytest.fixture(scope="module")
@@ -22,23 +18,8 @@ def pose():
     return m
 
 
-def _fixture():
-    return dict(np.load(POSES))
-
-
-def _scene(i, n, noise, outliers, seed):
-    f = _fixture()
-    rng = np.random.default_rng(seed)
-    p0, p1, _ = PR.synthetic_pair(f["K0"][i], f["K1"][i], f["T_0to1"][i], n, noise, outliers, tuple(f["size0_hw"][i]),
-                                  tuple(f["size1_hw"][i]), rng)
-    return p0, p1, f["K0"][i], f["K1"][i], f["T_0to1"][i]
-
-
 def _check(got, want, p, n):
-    info = got["info"][p].cpu().numpy()
-    assert list(info) == list(want["info"]), (list(info), list(want["info"]))
-    assert np.array_equal(got["inliers"][p, :n].cpu().numpy(), want["mask"])
-    assert not got["inliers"][p, n:].any()
+    check_common(got, want, p, n)
     for k in ("R", "t", "E"):
         g = got[k][p].cpu().numpy()
         assert np.isfinite(g).all()
@@ -48,7 +29,7 @@ def _check(got, want, p, n):
 @pytest.mark.parametrize("n,outliers,thr,iters", [(5, 0.0, 1.0, 1000), (6, 0.0, 2.5, 1000), (300, 0.3, 1.0, 1000), (300, 0.8, 2.5, 10000),
                                                   (2000, 0.5, 1.0, 1000), (4096, 0.6, 2.5, 10000), (2000, 0.0, 1.0, 10000)])
 def test_single_pair_equals_the_restatement(pose, n, outliers, thr, iters):
-    p0, p1, K0, K1, _ = _scene(7, n, 0.7, outliers, seed=n)
+    p0, p1, _, K0, K1, _ = scene(7, n, 0.7, outliers, seed=n)
     got = pose.estimate_relative_pose_batch(torch.from_numpy(p0)[None].cuda(), torch.from_numpy(p1)[None].cuda(), None, K0, K1, thr,
                                             max_iterations=iters, seed=11)
     torch.cuda.synchronize()
@@ -62,7 +43,7 @@ def test_ragged_batch_equals_the_restatement_pair_by_pair(pose):
     pts0, pts1 = np.zeros((P, cap, 2), np.float32), np.zeros((P, cap, 2), np.float32)
     K0, K1, sc = np.zeros((P, 3, 3)), np.zeros((P, 3, 3)), []
     for p, n in enumerate(ns):
-        a, b, k0, k1, _ = _scene(100 + p, max(n, 1), 0.5, 0.4, seed=p)
+        a, b, _, k0, k1, _ = scene(100 + p, max(n, 1), 0.5, 0.4, seed=p)
         pts0[p, :n], pts1[p, :n], K0[p], K1[p] = a[:n], b[:n], k0, k1
     got = pose.estimate_relative_pose_batch(torch.from_numpy(pts0).cuda(), torch.from_numpy(pts1).cuda(), torch.tensor(ns, dtype=torch.int32),
                                             K0, K1, 1.0, seed=5)
@@ -80,7 +61,7 @@ def test_index_list_entry_equals_gathered_points(pose):
     nm = np.array([500, 333, 20], np.int32)
     f = _fixture()
     for p in range(P):
-        a, b, _, _, _ = _scene(p, K, 0.5, 0.3, seed=p)
+        a, b, _, _, _, _ = scene(p, K, 0.5, 0.3, seed=p)
         kp0[p], kp1[p] = a, b[rng.permutation(K)]
         idx0[p] = rng.choice(K, cap, replace=False)
         idx1[p] = rng.choice(K, cap, replace=False)
@@ -126,7 +107,7 @@ def test_degenerate_inputs_do_not_fault_or_nan(pose):
 
 
 def test_same_seed_same_bits(pose):
-    p0, p1, K0, K1, _ = _scene(3, 1500, 1.0, 0.5, seed=1)
+    p0, p1, _, K0, K1, _ = scene(3, 1500, 1.0, 0.5, seed=1)
     a = pose.estimate_relative_pose_batch(torch.from_numpy(p0)[None].cuda(), torch.from_numpy(p1)[None].cuda(), None, K0, K1, 1.0, seed=4)
     b = pose.estimate_relative_pose_batch(torch.from_numpy(p0)[None].cuda(), torch.from_numpy(p1)[None].cuda(), None, K0, K1, 1.0, seed=4)
     torch.cuda.synchronize()
@@ -156,7 +137,7 @@ def test_megadepth1500_synthetic_auc(pose):
 
 
 def test_poselib_shaped_wrapper_equals_the_batch_entry(pose):
-    p0, p1, K0, K1, _ = _scene(11, 800, 0.5, 0.3, seed=2)
+    p0, p1, _, K0, K1, _ = scene(11, 800, 0.5, 0.3, seed=2)
     cam = lambda K: {"model": "PINHOLE", "width": 1600, "height": 1200, "params": [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]}   # noqa: E731
     pz, det = pose.estimate_relative_pose(p0, p1, cam(K0), cam(K1), {"max_epipolar_error": 1.5}, {})
     r = pose.estimate_relative_pose_batch(torch.from_numpy(p0)[None].cuda(), torch.from_numpy(p1)[None].cuda(), None, K0, K1, 1.5,

@@ -6,23 +6,7 @@ import pytest
 from scipy import integrate
 
 from oracle import homography_oracle as ho
-
-
-def synthetic_pair(n, outlier_frac, noise, seed, size=(640.0, 480.0)):
-    """n correspondences under a random plausible homography: (p0, p1, H_true, inlier flags)."""
-    g = np.random.default_rng(seed)
-    w, h = size
-    a = g.uniform(-0.35, 0.35)
-    s = g.uniform(0.8, 1.25)
-    H = np.array([[s * np.cos(a), -s * np.sin(a), g.uniform(-60, 60)],
-                  [s * np.sin(a), s * np.cos(a), g.uniform(-40, 40)],
-                  [g.uniform(-2e-4, 2e-4), g.uniform(-2e-4, 2e-4), 1.0]])
-    p0 = np.stack([g.uniform(0, w, n), g.uniform(0, h, n)], axis=1)
-    q = np.concatenate([p0, np.ones((n, 1))], axis=1) @ H.T
-    p1 = q[:, :2] / q[:, 2:] + g.normal(0, noise, (n, 2))
-    out = g.random(n) < outlier_frac
-    p1[out] = np.stack([g.uniform(0, w, out.sum()), g.uniform(0, h, out.sum())], axis=1)
-    return p0.astype(np.float32), p1.astype(np.float32), H, ~out
+from twoview_support import homography_pair as synthetic_pair
 
 
 def transfer_error(H, Ht, size=(640.0, 480.0)):

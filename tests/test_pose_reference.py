@@ -1,35 +1,15 @@
 """The relative-pose restatement (tests/pose_reference.py) against ground truth, and the evaluation metrics of accelerated_features_amd.pose
 on hand-computed cases.  CPU only: the restatement is what the GPU tests hold the kernels to, so it is checked here on its own."""
-import os
-
 import numpy as np
 import pytest
 
 import pose_reference as PR
+import twoview_support as TS
 from accelerated_features_amd.pose import pose_auc, relative_pose_error
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-POSES = os.path.join(HERE, "golden", "megadepth1500_poses.npz")
-
-
-def _rot(w):
-    th = np.linalg.norm(w)
-    k = w / th
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
 
 
 def _samples(rng, H):
-    x = np.zeros((4, H, 5))
-    gt = []
-    for h in range(H):
-        R, t = _rot(rng.normal(size=3) * 0.3), rng.normal(size=3)
-        t /= np.linalg.norm(t)
-        X = np.c_[rng.uniform(-1, 1, (5, 2)), rng.uniform(2, 6, 5)]
-        X2 = X @ R.T + t
-        x[0, h], x[1, h], x[2, h], x[3, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2], X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
-        gt.append((R, t))
-    return x, gt
+    return TS.true_samples(rng, H, 5, unit_t=True)
 
 
 def test_every_candidate_is_an_essential_matrix_through_the_sample():
@@ -92,7 +72,7 @@ def test_relative_pose_error_hand_cases():
     T[:3, 3] = [1.0, 0.0, 0.0]
     assert relative_pose_error(T, np.eye(3), [1.0, 0.0, 0.0]) == (0.0, 0.0)
     assert relative_pose_error(T, np.eye(3), [-2.0, 0.0, 0.0])[0] == 0.0                  # the sign of t is not observable
-    te, re = relative_pose_error(T, _rot(np.array([0.0, 0.0, np.deg2rad(10.0)])), [1.0, 1.0, 0.0])
+    te, re = relative_pose_error(T, TS.rotation(np.array([0.0, 0.0, np.deg2rad(10.0)])), [1.0, 1.0, 0.0])
     assert abs(te - 45.0) < 1e-9 and abs(re - 10.0) < 1e-9
     te, _ = relative_pose_error(T, np.eye(3), [0.0, 1.0, 0.0])
     assert abs(te - 90.0) < 1e-9
@@ -113,11 +93,11 @@ def test_pose_auc_hand_cases():
 
 @pytest.mark.parametrize("outliers", [0.0, 0.3, 0.6])
 def test_estimator_recovers_fixture_poses(outliers):
-    f = dict(np.load(POSES))
+    f = TS.fixture()
     rng = np.random.default_rng(int(outliers * 10))
     errs = []
     for p in range(0, 1500, 150):
-        a, b, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], 600, 0.7, outliers, tuple(f["size0_hw"][p]), tuple(f["size1_hw"][p]), rng)
+        a, b, _ = TS.fixture_pair(f, p, 600, 0.7, outliers, rng)
         r = PR.estimate(a, b, f["K0"][p], f["K1"][p], 1.0, max_iterations=2000, seed=3, pair=p)
         assert r["info"][0] == 1
         assert abs(np.linalg.norm(r["t"]) - 1.0) < 1e-12
@@ -138,7 +118,7 @@ def test_estimator_degenerate_inputs():
 
 def test_megadepth_synthetic_auc_on_every_10th_pair():
     """Where the GPU test's AUC floors come from: the restatement on every 10th pair of the same synthetic set clears them with margin."""
-    f = dict(np.load(POSES))
+    f = TS.fixture()
     pts0, pts1, counts = PR.megadepth_synthetic(f)
     err = []
     for p in range(0, 1500, 10):

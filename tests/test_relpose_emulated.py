@@ -1,48 +1,18 @@
 """relpose_solve (csrc/k_relpose.hip, on the shared geometry of csrc/twoview_math.hpp) compiled for the HOST (tests/emu/relpose_emu.cpp,
 fp contraction off) against the numpy restatement tests/pose_reference.py: on random, noise-free, noisy and near-degenerate samples the
 candidate poses must be equal bit for bit."""
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import pose_reference as PR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "accelerated_features_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-
-
-def _between(name, begin, end):
-    """(whole text, text between the two markers) of a product source file."""
-    t = open(os.path.join(CSRC, name)).read()
-    a = t.index(begin)
-    return t, t[a:t.index(end, a)]
-
-
-def _slice():
-    """The shared geometry (twoview_math.hpp, which must be host-compilable as a whole file) in front of the solver's own slice."""
-    header, shared = _between("twoview_math.hpp", "// ---- twoview math begin", "// ---- twoview math end")
-    _, solver = _between("k_relpose.hip", "// ---- solver begin", "// ---- solver end")
-    for s in (header, solver):
-        assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
-    assert "gauss_jordan" in shared and "gauss_jordan(S s" not in solver
-    return (shared + solver).replace("__device__ ", "")
+import twoview_support as TS
 
 
 @pytest.fixture(scope="module")
 def emu_bin():
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang")
-    td = tempfile.mkdtemp()
-    open(os.path.join(td, "relpose_slice.hpp"), "w").write(_slice())
-    out = os.path.join(td, "relpose_emu")
-    subprocess.run([CLANG, "-O2", "-w", "-std=c++20", "-ffp-contract=off", "-I", td, "-I", EMU, os.path.join(EMU, "relpose_emu.cpp"), "-o", out],
-                   check=True)
-    return out
+    return TS.build_emu("relpose_slice.hpp", "relpose_emu", TS.slice_solver("k_relpose.hip", "// ---- solver begin", "// ---- solver end"))
 
 
 def _run(emu_bin, x1, y1, x2, y2):
@@ -54,32 +24,18 @@ def _run(emu_bin, x1, y1, x2, y2):
     return cand, nc
 
 
+def _degenerate(X, sub):
+    if sub == 0:
+        X[:, 2] = 4.0 + 0.0 * X[:, 0]          # coplanar (fronto-parallel plane)
+    elif sub == 1:
+        X[:, 1] = X[:, 0] * 0.5                 # points on a plane through the centre
+    else:
+        X[4] = X[3] * (1 + 1e-9)                # a repeated point
+
+
 def _samples(rng, H):
     """Random samples of four kinds: uniform noise, noise-free scenes, noisy scenes, near-degenerate (coplanar / collinear / repeated)."""
-    x = rng.uniform(-0.8, 0.8, (4, H, 5))
-    kind = np.arange(H) % 4
-    for h in np.nonzero(kind > 0)[0]:
-        w = rng.normal(size=3) * 0.3
-        th = np.linalg.norm(w)
-        k = w / th
-        Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-        R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
-        t = rng.normal(size=3)
-        X = np.c_[rng.uniform(-1, 1, (5, 2)), rng.uniform(2, 6, 5)]
-        if kind[h] == 3:
-            sub = h % 3
-            if sub == 0:
-                X[:, 2] = 4.0 + 0.0 * X[:, 0]          # coplanar (fronto-parallel plane)
-            elif sub == 1:
-                X[:, 1] = X[:, 0] * 0.5                 # points on a plane through the centre
-            else:
-                X[4] = X[3] * (1 + 1e-9)                # a repeated point
-        X2 = X @ R.T + t
-        x[0, h], x[1, h] = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2]
-        x[2, h], x[3, h] = X2[:, 0] / X2[:, 2], X2[:, 1] / X2[:, 2]
-        if kind[h] == 2:
-            x[:, h] += rng.normal(size=(4, 5)) * 1e-3
-    return x
+    return TS.mixed_samples(rng, H, 5, 0.8, _degenerate)
 
 
 def test_host_solver_equals_the_restatement_bit_for_bit(emu_bin):

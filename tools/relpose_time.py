@@ -6,42 +6,19 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from accelerated_features_amd.pose import estimate_relative_pose_batch, pose_auc, relative_pose_error  # noqa: E402
-import pose_reference as PR  # noqa: E402
-
-f = dict(np.load(os.path.join(ROOT, "tests", "golden", "megadepth1500_poses.npz")))
+from twoview_support import time_megadepth  # noqa: E402
 
 
-def batch(P, nlo, nhi, seed):
-    rng = np.random.default_rng(seed)
-    cap = nhi
-    pts0, pts1 = np.zeros((P, cap, 2), np.float32), np.zeros((P, cap, 2), np.float32)
-    counts = rng.integers(nlo, nhi + 1, P).astype(np.int32)
-    for p in range(P):
-        a, b, _ = PR.synthetic_pair(f["K0"][p], f["K1"][p], f["T_0to1"][p], int(counts[p]), rng.uniform(0.5, 1.0), 0.4, tuple(f["size0_hw"][p]),
-                                    tuple(f["size1_hw"][p]), rng)
-        pts0[p, :counts[p]], pts1[p, :counts[p]] = a, b
-    return torch.from_numpy(pts0).cuda(), torch.from_numpy(pts1).cuda(), torch.from_numpy(counts).cuda()
-
-
-for P, nlo, nhi, iters, reps in ((1, 2000, 2000, 1000, 20), (1500, 200, 1024, 1000, 3), (1500, 200, 1024, 10000, 2)):
-    a, b, c = batch(P, nlo, nhi, 1500)
-    K0, K1 = f["K0"][:P], f["K1"][:P]
-    r = estimate_relative_pose_batch(a, b, c, K0, K1, 1.0, max_iterations=iters)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        r = estimate_relative_pose_batch(a, b, c, K0, K1, 1.0, max_iterations=iters)
-    e1.record()
-    torch.cuda.synchronize()
-    info, R, t = r["info"].cpu().numpy(), r["R"].cpu().numpy(), r["t"].cpu().numpy()
+def auc(f, P, r, info):
+    R, t = r["R"].cpu().numpy(), r["t"].cpu().numpy()
     err = [max(relative_pose_error(f["T_0to1"][p], R[p], t[p])) if info[p, 0] else np.inf for p in range(P)]
-    print(f"P {P:4d} n {nlo}-{nhi} max_iterations {iters:5d}: {e0.elapsed_time(e1) / reps:9.3f} ms per call, found {int(info[:, 0].sum())}/{P}, "
-          f"loop iterations mean {info[:, 2].mean():.0f} max {info[:, 2].max()}, refinement steps {info[:, 4].mean():.1f}, AUC {pose_auc(err)}",
-          flush=True)
+    return f"AUC {pose_auc(err)}"
+
+
+time_megadepth(lambda a, b, c, f, P, iters: estimate_relative_pose_batch(a, b, c, f["K0"][:P], f["K1"][:P], 1.0, max_iterations=iters),
+               "max_iterations", auc)
