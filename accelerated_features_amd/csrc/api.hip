@@ -913,6 +913,54 @@ int xfh_estimate_relpose_matches(const float* kpts0, const float* kpts1, int kpt
                                  min_iters, max_iters, success_prob, seed, R, t, E, mask, info, workspace, workspace_bytes, stream);
 }
 
+size_t xfh_relpose_sweep_workspace_bytes(int P, int max_iters, int T) {
+    if (P <= 0 || max_iters <= 0 || T < 1 || T > 16) return 0;
+    return xfh::relpose_sweep_workspace_bytes(P, max_iters, T);
+}
+
+static int estimate_relpose_sweep_impl(const char* who, const float* pts0, const float* pts1, const int64_t* idx0, const int64_t* idx1, int kcap,
+                                       const int32_t* counts, int n_const, int P, int cap, const double* K0, const double* K1,
+                                       const double* max_epipolar_errors, int T, int min_iters, int max_iters, double success_prob, uint64_t seed,
+                                       double* R, double* t, double* E, uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes,
+                                       xfh_stream stream) {
+    if (!pts0 || !pts1 || !K0 || !K1 || !max_epipolar_errors || !R || !t || !E || !mask || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (P <= 0 || P > 65535 || cap <= 0 || cap > (1 << 24) || kcap <= 0 || (!counts && (n_const < 0 || n_const > cap)))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, n %d)", who, P, cap, n_const);
+    if (T < 1 || T > 16) return fail(XFH_ERR_ARG, "%s: %d thresholds outside [1, 16]", who, T);
+    for (int j = 0; j < T; ++j)
+        if (!(max_epipolar_errors[j] > 0.0) || !std::isfinite(max_epipolar_errors[j]))
+            return fail(XFH_ERR_ARG, "%s: threshold %d is %g", who, j, max_epipolar_errors[j]);
+    if (!(success_prob > 0.0 && success_prob < 1.0) || min_iters < 0)
+        return fail(XFH_ERR_ARG, "%s: success_prob %g / min_iters %d", who, success_prob, min_iters);
+    if (max_iters < 1 || max_iters > 16384) return fail(XFH_ERR_UNSUPPORTED, "%s: max_iters %d outside [1, 16384]", who, max_iters);
+    int rc = check_ws(workspace, workspace_bytes, xfh::relpose_sweep_workspace_bytes(P, max_iters, T));
+    if (rc) return rc;
+    if (launch_estimate_relpose_sweep(pts0, pts1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, max_epipolar_errors, T, min_iters, max_iters,
+                                      success_prob, seed, R, t, E, mask, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: unsupported configuration", who);
+    return check_launch(who);
+}
+
+int xfh_estimate_relpose_sweep(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap, const double* K0,
+                               const double* K1, const double* max_epipolar_errors, int T, int min_iters, int max_iters, double success_prob,
+                               uint64_t seed, double* R, double* t, double* E, uint8_t* mask, int32_t* info, void* workspace,
+                               size_t workspace_bytes, xfh_stream stream) {
+    return estimate_relpose_sweep_impl("xfh_estimate_relpose_sweep", pts0, pts1, nullptr, nullptr, cap, counts, n_const, P, cap, K0, K1,
+                                       max_epipolar_errors, T, min_iters, max_iters, success_prob, seed, R, t, E, mask, info, workspace,
+                                       workspace_bytes, stream);
+}
+
+int xfh_estimate_relpose_sweep_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                                       const int32_t* n_matches, int P, int cap, const double* K0, const double* K1,
+                                       const double* max_epipolar_errors, int T, int min_iters, int max_iters, double success_prob, uint64_t seed,
+                                       double* R, double* t, double* E, uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes,
+                                       xfh_stream stream) {
+    if (!idx0 || !idx1 || !n_matches) return fail(XFH_ERR_ARG, "xfh_estimate_relpose_sweep_matches: NULL argument");
+    return estimate_relpose_sweep_impl("xfh_estimate_relpose_sweep_matches", kpts0, kpts1, idx0, idx1, kpt_cap, n_matches, 0, P, cap, K0, K1,
+                                       max_epipolar_errors, T, min_iters, max_iters, success_prob, seed, R, t, E, mask, info, workspace,
+                                       workspace_bytes, stream);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

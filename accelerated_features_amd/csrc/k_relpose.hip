@@ -48,6 +48,27 @@
 //   relpose_bound_kernel  : the bound the loop reaches from the records among the first 256; the later blocks are solved and scored
 //                           only below max(min_iterations, bound)
 //   relpose_select_kernel : one workgroup per pair: stopping rule over the cost list (tiles in LDS), refinement, mask, outputs
+//
+// The threshold sweep (xfh_estimate_relpose_sweep: the twelve RANSAC thresholds of modules/eval/scannet1500.py in one call).  Slice j of
+// a sweep IS the estimate above at threshold j -- the same specification, bit for bit.  What the T estimates share is computed once: a
+// hypothesis is a function of (seed, pair, it) alone, so one solve per hypothesis serves every threshold (candidate poses stored once,
+// 960 B), and the Sampson error of a (candidate, correspondence) is evaluated once and clamped T times.  Only the cost / count lists
+// (T x 120 B per hypothesis, (P, iters_pad, 10, T)), the bounds and the select step are per threshold:
+//   relpose_sweep_zero_kernel  : the lists, candidate counts zeroed
+//   relpose_solve_kernel       : unchanged; the later blocks are solved below the pair's LARGEST bound over the thresholds
+//   relpose_sweep_score_kernel : as relpose_score_kernel, T costs and T counts per residual.  The thresholds arrive sorted in descending
+//                                order (the host sorts; `slot` maps threshold j to its place), so the T tests nest: a residual at or above
+//                                the largest threshold -- most of them, under a wrong model -- takes one comparison.  Such a residual costs exactly
+//                                2^20 (thr2 / thr2 = 1), so only the inliers' costs rp_cost(r2, thr2_j), division included, are summed and
+//                                2^20 x (residuals - inliers) is added at the end; integer sums, the same total.  The accumulators stay in
+//                                registers: the nest is unrolled at compile time over a padded size (4, 8, 12, 16; padding: thr2 = 0,
+//                                never taken)
+//   relpose_bound_kernel       : one bound per (pair, threshold) from the records among the first 256, and their maximum per pair
+//   relpose_select_kernel      : one workgroup per (pair, threshold) on that threshold's lists (stride T); the single call is T = 1
+// Hypotheses that the sweep solves and scores at or beyond threshold j's own bound (below the pair's largest) do not change slice j:
+// rs::scan_stopping_rule never looks at an entry at or beyond the loop's stop, and that stop is at most threshold j's bound when the
+// loop runs past the first 256 hypotheses (every record among them is one the loop sees) and lies inside the first 256 -- which are
+// always solved and scored -- otherwise.
 #include "ransac_common.hpp"
 #include "twoview_math.hpp"
 
@@ -56,7 +77,7 @@
 namespace xfh {
 namespace rp {
 using rs::HYP_PER_WG, rs::PTS_PER_WG, rs::SEL_TILE, rs::SEL_CACHE;
-constexpr int LO_ITERS = 10, MAX_ITERS = 16384, MAX_CAND = 10;
+constexpr int LO_ITERS = 10, MAX_ITERS = 16384, MAX_THR = 16, MAX_CAND = 10;
 constexpr int SLICE = 280, SOLVE_WG = 64, NSUM = 20;
 }  // namespace rp
 
@@ -393,13 +414,17 @@ struct RpArgs {
     const double* K1;
     int n_const, P, cap, kcap, iters, iters_pad, min_iters;
     int chunk;
-    double max_err, log1mp;
+    int T;                    // thresholds (1: the single call); outputs are (P, T, ...)
+    double max_err[rp::MAX_THR];        // in descending order
+    unsigned char slot[rp::MAX_THR];    // threshold j of the caller is max_err[slot[j]]
+    double log1mp;
     unsigned long long seed;
     double* cand;             // (P, iters_pad, 10, 12)
-    unsigned long long* hcost;   // (P, iters_pad, 10)
-    unsigned* hcnt;              // (P, iters_pad, 10)
+    unsigned long long* hcost;   // (P, iters_pad, 10, T)
+    unsigned* hcnt;              // (P, iters_pad, 10, T)
     int* ncand;                  // (P, iters_pad)
-    int* bound;                  // (P)
+    int* bound;                  // (P, T)
+    int* bound_max;              // (P): the largest over the thresholds (T = 1: bound itself)
     double* R;
     double* t;
     double* E;
@@ -411,13 +436,18 @@ struct RpArgs {
 struct RpPair {
     rs::PairView pts;
     double fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1, thr2;
-    __device__ RpPair(const RpArgs& a, int pair) : pts(a, pair) {
+    // thr2: of threshold max_err[slot]
+    __device__ RpPair(const RpArgs& a, int pair, int slot = 0) : pts(a, pair) {
         const double* k0 = a.K0 + (size_t)pair * 9;
         const double* k1 = a.K1 + (size_t)pair * 9;
         fx0 = k0[0]; cx0 = k0[2]; fy0 = k0[4]; cy0 = k0[5];
         fx1 = k1[0]; cx1 = k1[2]; fy1 = k1[4]; cy1 = k1[5];
-        const double thr = a.max_err / (0.5 * ((fx0 + fy0) * 0.5 + (fx1 + fy1) * 0.5));
-        thr2 = thr * thr;
+        thr2 = thr2_of(a.max_err[slot]);
+    }
+    // the squared threshold in normalised units
+    __device__ inline double thr2_of(double max_err) const {
+        const double thr = max_err / (0.5 * ((fx0 + fy0) * 0.5 + (fx1 + fy1) * 0.5));
+        return thr * thr;
     }
     // normalised coordinates (x1, y1, x2, y2) of correspondence i
     __device__ inline double4 get(int i) const {
@@ -437,7 +467,7 @@ __global__ __launch_bounds__(64) void relpose_solve_kernel(RpArgs a, int it_base
     const int it = it_base + blockIdx.x * rp::SOLVE_WG + tid;
     const int n = rs::pair_count(a, pair);
     if (n < 5 || it >= a.iters) return;
-    if (use_bound && a.bound[pair] <= it) return;
+    if (use_bound && a.bound_max[pair] <= it) return;
     const RpPair pp(a, pair);
     int idx[5] = {-1, -1, -1, -1, -1};
     if (!rs::sample_distinct(a.seed, pair, it, n, idx)) return;
@@ -491,17 +521,95 @@ __global__ __launch_bounds__(256) void relpose_score_kernel(RpArgs a, int blk0, 
     }
 }
 
+// ---- the threshold sweep's zero and score ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void relpose_sweep_zero_kernel(RpArgs a, size_t nhyp) {
+    const size_t nlist = nhyp * rp::MAX_CAND * a.T;
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nlist; j += (size_t)gridDim.x * 256) {
+        a.hcost[j] = 0ull; a.hcnt[j] = 0u;
+        if (j < nhyp) a.ncand[j] = 0;
+    }
+}
+
+// r2 against thresholds J.. of the descending list: cost and count of the inliers only
+template <int J, int TP>
+__device__ inline void rp_sweep_add(double r2, const double (&thr2)[TP], unsigned (&sc)[TP], unsigned (&cnt)[TP]) {
+    if constexpr (J < TP) {
+        if (r2 < thr2[J]) {
+            sc[J] += rp_cost(r2, thr2[J]);
+            ++cnt[J];
+            rp_sweep_add<J + 1, TP>(r2, thr2, sc, cnt);
+        }
+    }
+}
+
+// relpose_score_kernel for a.T <= TP thresholds at once (the lists in the order of a.max_err).  A chunk holds at most PTS_PER_WG = 512
+// correspondences and an inlier costs less than 2^20, so the inliers' cost of a chunk fits 32 bits.
+template <int TP>
+__global__ __launch_bounds__(256) void relpose_sweep_score_kernel(RpArgs a, int blk0, int use_bound) {
+    __shared__ double4 spt[rp::PTS_PER_WG];
+    const int pair = blockIdx.z, tid = threadIdx.x;
+    const int n = rs::pair_count(a, pair);
+    const int c0 = blockIdx.y * a.chunk;
+    const int it0 = (blockIdx.x + blk0) * rp::HYP_PER_WG;
+    if (n < 5 || c0 >= n) return;
+    if (use_bound && a.bound_max[pair] <= it0) return;
+    const RpPair pp(a, pair);
+    double thr2[TP];
+#pragma unroll
+    for (int j = 0; j < TP; ++j) thr2[j] = j < a.T ? pp.thr2_of(a.max_err[j]) : 0.0;
+    const int c1 = min(c0 + a.chunk, n);
+    for (int i = tid; i < c1 - c0; i += 256) spt[i] = pp.get(c0 + i);
+    __syncthreads();
+    const int it = it0 + tid;
+    if (it >= a.iters) return;
+    const size_t h = (size_t)pair * a.iters_pad + it;
+    const int nc = a.ncand[h];
+    const int m = c1 - c0;
+    for (int c = 0; c < nc; ++c) {
+        const double* o = a.cand + (h * rp::MAX_CAND + c) * rp::CAND_DOUBLES;
+        double Rm[9], tv[3], E[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rm[k] = o[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tv[k] = o[9 + k];
+        rp_pose_E(Rm, tv, E);
+        unsigned sc[TP], cnt[TP];
+#pragma unroll
+        for (int j = 0; j < TP; ++j) { sc[j] = 0u; cnt[j] = 0u; }
+#pragma unroll 2
+        for (int i = 0; i < m; ++i) {
+            const double4 q = spt[i];
+            rp_sweep_add<0, TP>(tv::sampson(E, q.x, q.y, q.z, q.w), thr2, sc, cnt);
+        }
+        const size_t l = (h * rp::MAX_CAND + c) * a.T;
+#pragma unroll
+        for (int j = 0; j < TP; ++j)
+            if (j < a.T) {
+                atomicAdd(a.hcost + l + j, (unsigned long long)sc[j] + ((unsigned long long)(m - (int)cnt[j]) << 20));
+                atomicAdd(a.hcnt + l + j, cnt[j]);
+            }
+    }
+}
+
 // After the first 256 hypotheses: the index below which the loop can still visit hypotheses = max(min_iters, rs::hypotheses_bound over
 // the records (strict prefix minima of the cost) among them); a hypothesis costs the minimum over its candidates (rs::hyp_best)
+// -- per threshold, and the largest of them per pair (what the later blocks are solved and scored below)
 __global__ __launch_bounds__(256) void relpose_bound_kernel(RpArgs a) {
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int n = rs::pair_count(a, pair);
-    unsigned long long cost = ~0ull;
-    unsigned cnt = 0;
-    int cand = 0;
-    const bool has = tid < a.iters && n >= 5 && rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost, a.hcnt, (size_t)pair * a.iters_pad + tid, cost, cnt, cand);
-    const int bmin = rs::hypotheses_bound<5, true>(has, cost, cnt, n, a.log1mp, a.iters);
-    if (tid == 0) a.bound[pair] = bmin > a.min_iters ? bmin : a.min_iters;
+    int bmax = 0;
+    for (int j = 0; j < a.T; ++j) {
+        unsigned long long cost = ~0ull;
+        unsigned cnt = 0;
+        int cand = 0;
+        const bool has = tid < a.iters && n >= 5 && rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost + j, a.hcnt + j, (size_t)pair * a.iters_pad + tid, cost, cnt, cand, a.T);
+        const int bmin = rs::hypotheses_bound<5, true>(has, cost, cnt, n, a.log1mp, a.iters);
+        const int b = bmin > a.min_iters ? bmin : a.min_iters;
+        if (tid == 0) a.bound[pair * a.T + j] = b;
+        bmax = b > bmax ? b : bmax;
+        __syncthreads();                                     // hypotheses_bound's shared words read by everybody before the next threshold
+    }
+    if (tid == 0) a.bound_max[pair] = bmax;
 }
 
 // ---- selection, refinement, mask --------------------------------------------------------------------------------------------------------
@@ -568,35 +676,38 @@ __device__ inline void rp_tangent(const double* t, double* b1, double* b2) {
     tv::cross3(t, b1, b2);
 }
 
+// workgroup (pair, j): threshold j of the caller on its own cost / count lists
 __global__ __launch_bounds__(256) void relpose_select_kernel(RpArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ double pose_sh[12];
     __shared__ unsigned long long sc_sh;
     __shared__ unsigned cnt_sh;
     const int pair = blockIdx.x, tid = threadIdx.x;
+    const int slot = a.slot[blockIdx.y];
+    const size_t out = (size_t)pair * a.T + blockIdx.y;
     const int n = rs::pair_count(a, pair);
-    unsigned char* mask = a.mask + (size_t)pair * a.cap;
-    int32_t* info = a.info + pair * 8;
+    unsigned char* mask = a.mask + out * a.cap;
+    int32_t* info = a.info + out * 8;
 
     // ---- the stopping rule of the sequential loop, over tiles of the cost list
     int best, best_cand, iters_run;
     rs::scan_stopping_rule<5, true>(lds_raw, n, a.iters, a.min_iters, a.log1mp,
                                     [&](int it, unsigned long long& c, unsigned& k, int& cd) {
-                                        return rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost, a.hcnt, (size_t)pair * a.iters_pad + it, c, k, cd);
+                                        return rs::hyp_best<rp::MAX_CAND, true>(a.ncand, a.hcost + slot, a.hcnt + slot, (size_t)pair * a.iters_pad + it, c, k, cd, a.T);
                                     },
                                     best, best_cand, iters_run);
     if (best >= 0 && tid < 12) pose_sh[tid] = a.cand[(((size_t)pair * a.iters_pad + best) * rp::MAX_CAND + best_cand) * rp::CAND_DOUBLES + tid];
     __syncthreads();
-    double* Rout = a.R + (size_t)pair * 9;
-    double* tout = a.t + (size_t)pair * 3;
-    double* Eout = a.E + (size_t)pair * 9;
+    double* Rout = a.R + out * 9;
+    double* tout = a.t + out * 3;
+    double* Eout = a.E + out * 9;
     if (best < 0) {
         rs::write_nothing_found(mask, a.cap, info, iters_run, n);
         if (tid < 9) { Rout[tid] = 0.0; Eout[tid] = 0.0; }
         if (tid < 3) tout[tid] = 0.0;
         return;
     }
-    const RpPair pp(a, pair);
+    const RpPair pp(a, pair, slot);
     const double thr2 = pp.thr2;
     double* red = reinterpret_cast<double*>(lds_raw);         // the tiles are dead: reduction buffer from here on
     double4* spt = reinterpret_cast<double4*>(lds_raw + (rs::block_sums_bytes(rp::NSUM) + 31 & ~(size_t)31));
@@ -679,45 +790,82 @@ size_t relpose_workspace_bytes(int P, int max_iters) {
     const size_t per = (size_t)rp::MAX_CAND * rp::CAND_DOUBLES * 8 + (size_t)rp::MAX_CAND * 12 + 4;
     return (size_t)P * pad * per + (size_t)P * 4 + 1024;
 }
+size_t relpose_sweep_workspace_bytes(int P, int max_iters, int T) {
+    const size_t pad = (size_t)ceil_div(max_iters, 256) * 256;
+    const size_t per = (size_t)rp::MAX_CAND * rp::CAND_DOUBLES * 8 + (size_t)T * rp::MAX_CAND * 12 + 4;
+    return (size_t)P * pad * per + (size_t)P * (T + 1) * 4 + 1024;
+}
 
-int launch_estimate_relpose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
-                            int P, int cap, const double* K0, const double* K1, double max_err, int min_iters, int max_iters, double success_prob,
-                            unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info, void* ws, hipStream_t st) {
-    if (max_iters < 1 || max_iters > rp::MAX_ITERS || P > 65535) return -1;
+// T thresholds in the caller's order; T = 1 is the single call, kernel for kernel
+int launch_estimate_relpose_sweep(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
+                                  int P, int cap, const double* K0, const double* K1, const double* max_errs, int T, int min_iters, int max_iters,
+                                  double success_prob, unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info,
+                                  void* ws, hipStream_t st) {
+    if (max_iters < 1 || max_iters > rp::MAX_ITERS || P > 65535 || T < 1 || T > rp::MAX_THR) return -1;
     RpArgs a;
     a.p0 = p0; a.p1 = p1; a.idx0 = idx0; a.idx1 = idx1; a.kcap = idx0 ? kcap : cap; a.counts = counts; a.n_const = n_const; a.P = P; a.cap = cap;
     a.K0 = K0; a.K1 = K1; a.iters = max_iters; a.iters_pad = ceil_div(max_iters, 256) * 256; a.min_iters = min_iters < 0 ? 0 : min_iters;
-    a.max_err = max_err; a.log1mp = log(1.0 - success_prob); a.seed = seed;
+    a.log1mp = log(1.0 - success_prob); a.seed = seed;
+    a.T = T;
+    int order[rp::MAX_THR];                                  // the thresholds in descending order (stable: repeated values keep their order)
+    for (int j = 0; j < T; ++j) {
+        int k = j;
+        for (; k > 0 && max_errs[order[k - 1]] < max_errs[j]; --k) order[k] = order[k - 1];
+        order[k] = j;
+    }
+    for (int k = 0; k < rp::MAX_THR; ++k) { a.max_err[k] = k < T ? max_errs[order[k]] : 0.0; a.slot[k] = 0; }
+    for (int k = 0; k < T; ++k) a.slot[order[k]] = (unsigned char)k;
     unsigned char* w = static_cast<unsigned char*>(ws);
     const size_t nhyp = (size_t)P * a.iters_pad;
     a.cand = reinterpret_cast<double*>(w); w += nhyp * rp::MAX_CAND * rp::CAND_DOUBLES * 8;
-    a.hcost = reinterpret_cast<unsigned long long*>(w); w += nhyp * rp::MAX_CAND * 8;
-    a.hcnt = reinterpret_cast<unsigned*>(w); w += nhyp * rp::MAX_CAND * 4;
+    a.hcost = reinterpret_cast<unsigned long long*>(w); w += nhyp * rp::MAX_CAND * T * 8;
+    a.hcnt = reinterpret_cast<unsigned*>(w); w += nhyp * rp::MAX_CAND * T * 4;
     a.ncand = reinterpret_cast<int*>(w); w += nhyp * 4;
     a.bound = reinterpret_cast<int*>(w);
+    a.bound_max = T == 1 ? a.bound : a.bound + (size_t)P * T;
     a.R = R; a.t = t; a.E = E; a.mask = mask; a.info = info;
-    size_t zg = (nhyp + 255) / 256;
-    relpose_zero_kernel<<<(unsigned)(zg > 2048 ? 2048 : zg), 256, 0, st>>>(a, nhyp);
     a.chunk = rs::score_chunk(P, cap);
     const int nblk = ceil_div(max_iters, rp::HYP_PER_WG), nch = ceil_div(cap, a.chunk);
+    auto score = [&](int blocks, int blk0, int use_bound) {
+        const dim3 grid(blocks, nch, P);
+        if (T == 1) relpose_score_kernel<<<grid, 256, 0, st>>>(a, blk0, use_bound);
+        else if (T <= 4) relpose_sweep_score_kernel<4><<<grid, 256, 0, st>>>(a, blk0, use_bound);
+        else if (T <= 8) relpose_sweep_score_kernel<8><<<grid, 256, 0, st>>>(a, blk0, use_bound);
+        else if (T <= 12) relpose_sweep_score_kernel<12><<<grid, 256, 0, st>>>(a, blk0, use_bound);
+        else relpose_sweep_score_kernel<16><<<grid, 256, 0, st>>>(a, blk0, use_bound);
+    };
+    if (T == 1) {
+        const size_t zg = (nhyp + 255) / 256;
+        relpose_zero_kernel<<<(unsigned)(zg > 2048 ? 2048 : zg), 256, 0, st>>>(a, nhyp);
+    } else {
+        const size_t zg = (nhyp * rp::MAX_CAND * T + 255) / 256;
+        relpose_sweep_zero_kernel<<<(unsigned)(zg > 8192 ? 8192 : zg), 256, 0, st>>>(a, nhyp);
+    }
     const size_t solve_lds = (size_t)rp::SLICE * rp::SOLVE_WG * sizeof(double);
     static AttrMask attr_solve = 0, attr_sel = 0;
     set_max_dynamic_lds(reinterpret_cast<const void*>(relpose_solve_kernel), (int)solve_lds, attr_solve);
     const int first = max_iters < rp::HYP_PER_WG ? max_iters : rp::HYP_PER_WG;
     relpose_solve_kernel<<<dim3(ceil_div(first, rp::SOLVE_WG), P), rp::SOLVE_WG, solve_lds, st>>>(a, 0, 0);
-    relpose_score_kernel<<<dim3(1, nch, P), 256, 0, st>>>(a, 0, 0);
+    score(1, 0, 0);
     if (nblk > 1) {
         relpose_bound_kernel<<<P, 256, 0, st>>>(a);
         relpose_solve_kernel<<<dim3(ceil_div(max_iters - rp::HYP_PER_WG, rp::SOLVE_WG), P), rp::SOLVE_WG, solve_lds, st>>>(a, rp::HYP_PER_WG, 1);
-        relpose_score_kernel<<<dim3(nblk - 1, nch, P), 256, 0, st>>>(a, 1, 1);
+        score(nblk - 1, 1, 1);
     }
     const size_t red = (rs::block_sums_bytes(rp::NSUM) + 31) & ~(size_t)31;
     const size_t tiles = (size_t)rp::SEL_TILE * 16;
     const size_t front = red > tiles ? red : tiles;
     const size_t lds = (front > red ? front : red) + (size_t)rp::SEL_CACHE * sizeof(double4);
     set_max_dynamic_lds(reinterpret_cast<const void*>(relpose_select_kernel), (int)lds, attr_sel);
-    relpose_select_kernel<<<P, 256, lds, st>>>(a);
+    relpose_select_kernel<<<dim3(P, T), 256, lds, st>>>(a);
     return 0;
+}
+
+int launch_estimate_relpose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
+                            int P, int cap, const double* K0, const double* K1, double max_err, int min_iters, int max_iters, double success_prob,
+                            unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info, void* ws, hipStream_t st) {
+    return launch_estimate_relpose_sweep(p0, p1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, &max_err, 1, min_iters, max_iters, success_prob, seed,
+                                         R, t, E, mask, info, ws, st);
 }
 
 }  // namespace xfh

@@ -106,6 +106,12 @@ size_t relpose_workspace_bytes(int P, int max_iters);
 int launch_estimate_relpose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
                             int P, int cap, const double* K0, const double* K1, double max_err, int min_iters, int max_iters, double success_prob,
                             unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info, void* ws, hipStream_t st);
+// the same at T thresholds (host array) in one pass: outputs (P, T, ...)
+size_t relpose_sweep_workspace_bytes(int P, int max_iters, int T);
+int launch_estimate_relpose_sweep(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
+                                  int P, int cap, const double* K0, const double* K1, const double* max_errs, int T, int min_iters, int max_iters,
+                                  double success_prob, unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info,
+                                  void* ws, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

@@ -105,18 +105,20 @@ __device__ inline bool better(unsigned long long v, unsigned long long than) { r
 template <bool LOWER>
 __device__ inline unsigned long long worst() { return LOWER ? ~0ull : 0ull; }     // what no model is better than
 
-// value of hypothesis h = the best of its candidates' (the lower index on ties) and that candidate's inlier count; false: no model
+// value of hypothesis h = the best of its candidates' (the lower index on ties) and that candidate's inlier count; false: no model.
+// `stride`: entries per candidate in hval / hcnt (k_relpose.hip's threshold sweep keeps one per threshold and passes the lists offset
+// to its own)
 template <int MAX_CAND, bool LOWER>
 __device__ inline bool hyp_best(const int* ncand, const unsigned long long* hval, const unsigned* hcnt, size_t h, unsigned long long& val,
-                                unsigned& cnt, int& cand) {
+                                unsigned& cnt, int& cand, size_t stride = 1) {
     const int nc = ncand[h];
     if (nc <= 0) return false;
-    val = hval[h * MAX_CAND];
-    cnt = hcnt[h * MAX_CAND];
+    val = hval[h * MAX_CAND * stride];
+    cnt = hcnt[h * MAX_CAND * stride];
     cand = 0;
     for (int c = 1; c < nc; ++c) {
-        const unsigned long long v = hval[h * MAX_CAND + c];
-        if (better<LOWER>(v, val)) { val = v; cnt = hcnt[h * MAX_CAND + c]; cand = c; }
+        const unsigned long long v = hval[(h * MAX_CAND + c) * stride];
+        if (better<LOWER>(v, val)) { val = v; cnt = hcnt[(h * MAX_CAND + c) * stride]; cand = c; }
     }
     return true;
 }

@@ -329,6 +329,29 @@ int xfh_estimate_relpose_matches(const float* kpts0, const float* kpts1, int kpt
                                  void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Relative pose at T RANSAC thresholds in one pass -- the protocol of modules/eval/scannet1500.py, which runs
+ *     estimate_pose(kpts0, kpts1, K0, K1, thresh)
+ * over all pairs at twelve thresholds (0.5 ... 6.0 px).  Slice j of the result IS xfh_estimate_relpose at
+ * max_epipolar_errors[j] with the other arguments unchanged, bit for bit: a hypothesis does not depend on the threshold, so it
+ * is solved once and every Sampson error is evaluated once; only the cost lists, the stopping rule and the refinement are per
+ * threshold (DESIGN.md 3.10 / csrc/k_relpose.hip).
+ *   max_epipolar_errors: T values in pixels in HOST memory (read before the call returns), 1 <= T <= 16, each finite and
+ *   positive, in any order, repeats allowed.  The other inputs as for xfh_estimate_relpose.
+ *   R (P,T,9), t (P,T,3), E (P,T,9) fp64; mask (P,T,cap) uint8; info (P,T,8) int32, the same eight words per (pair, threshold).
+ *   xfh_estimate_relpose_sweep_matches: the same on the matcher's output (kpts + idx0/idx1 + n_matches).
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_relpose_sweep_workspace_bytes(int P, int max_iters, int T);
+int xfh_estimate_relpose_sweep(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap,
+                               const double* K0, const double* K1, const double* max_epipolar_errors, int T, int min_iters,
+                               int max_iters, double success_prob, uint64_t seed, double* R, double* t, double* E, uint8_t* mask,
+                               int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_estimate_relpose_sweep_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                                       const int32_t* n_matches, int P, int cap, const double* K0, const double* K1,
+                                       const double* max_epipolar_errors, int T, int min_iters, int max_iters, double success_prob,
+                                       uint64_t seed, double* R, double* t, double* E, uint8_t* mask, int32_t* info,
+                                       void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
