@@ -59,6 +59,10 @@ SIGNATURES = {
     "xfh_estimate_relpose_sweep": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_estimate_relpose_sweep_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p,
                                                 _p, _p, _sz, _p]),
+    "xfh_abspose_workspace_bytes": (_sz, [_i, _i]),
+    "xfh_estimate_abspose": (_i, [_p, _p, _p, _i, _i, _i, _p, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_estimate_abspose_matches": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _p, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p,
+                                          _sz, _p]),
     "xfh_fundamental_workspace_bytes": (_sz, [_i, _i]),
     "xfh_find_fundamental": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "xfh_find_fundamental_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz,

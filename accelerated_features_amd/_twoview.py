@@ -76,3 +76,33 @@ def run_chunked(who, P, limit, workspace_bytes, dev, call):
         off = (-ws.data_ptr()) % 256
         ws.record_stream(stream)
         _lib.check(call(a, b, C.c_void_p(ws.data_ptr() + off), ws.numel() - off, C.c_void_p(stream.cuda_stream)), who)
+
+
+def check_points_2d3d(what, pts2d, pts3d, counts):
+    """A (P, cap, 2) and a (P, cap, 3) point list (anything torch.as_tensor takes) and their counts or None -> float32 / int32 tensors on
+    the device."""
+    dev = pts2d.device if torch.is_tensor(pts2d) and pts2d.is_cuda else device(what)
+    pts2d = torch.as_tensor(pts2d).to(dev).float().contiguous()
+    pts3d = torch.as_tensor(pts3d).to(dev).float().contiguous()
+    if pts2d.dim() != 3 or pts2d.shape[2] != 2 or pts3d.dim() != 3 or pts3d.shape[2] != 3 or pts3d.shape[:2] != pts2d.shape[:2]:
+        raise RuntimeError('expected a (P, cap, 2) and a (P, cap, 3) point tensor of the same P and cap')
+    if counts is not None:
+        counts = torch.as_tensor(counts).to(dev).to(torch.int32).contiguous()
+        if counts.shape != (pts2d.shape[0],):
+            raise RuntimeError('counts must have one entry per pair')
+    return pts2d, pts3d, counts, dev
+
+
+def check_matches_2d3d(who, kpts2d, points3d, idx2d, idx3d, n_matches):
+    """Key-points (P,K2,2) float32, 3D points (P,K3,3) float32 (K2 and K3 independent), idx (P,cap) int64, n_matches (P,) int32, all
+    device-resident.  Returns (device, P, cap)."""
+    if not kpts2d.is_cuda:
+        raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
+    P, cap = idx2d.shape
+    if (kpts2d.dim() != 3 or points3d.dim() != 3 or kpts2d.shape[0] != P or points3d.shape[0] != P or kpts2d.shape[2] != 2
+            or points3d.shape[2] != 3 or idx3d.shape != idx2d.shape or n_matches.shape != (P,)):
+        raise RuntimeError('expected kpts (P,K2,2), points3d (P,K3,3), idx (P,cap), n_matches (P,)')
+    for t, dt in ((kpts2d, torch.float32), (points3d, torch.float32), (idx2d, torch.int64), (idx3d, torch.int64), (n_matches, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != kpts2d.device:
+            raise RuntimeError(f'{who}: contiguous float32 points, int64 indices, int32 counts on one device expected')
+    return kpts2d.device, P, cap

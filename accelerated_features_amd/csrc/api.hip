@@ -961,6 +961,45 @@ int xfh_estimate_relpose_sweep_matches(const float* kpts0, const float* kpts1, i
                                        workspace_bytes, stream);
 }
 
+size_t xfh_abspose_workspace_bytes(int P, int max_iters) {
+    if (P <= 0 || max_iters <= 0) return 0;
+    return xfh::abspose_workspace_bytes(P, max_iters);
+}
+
+static int estimate_abspose_impl(const char* who, const float* pts2d, const float* pts3d, const int64_t* idx2d, const int64_t* idx3d, int cap2, int cap3,
+                                 const int32_t* counts, int n_const, int P, int cap, const double* K, double max_reproj_error, int min_iters,
+                                 int max_iters, double success_prob, uint64_t seed, double* R, double* t, uint8_t* mask, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    if (!pts2d || !pts3d || !K || !R || !t || !mask || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (P <= 0 || P > 65535 || cap <= 0 || cap > (1 << 24) || cap2 <= 0 || cap3 <= 0 || (!counts && (n_const < 0 || n_const > cap)))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, n %d)", who, P, cap, n_const);
+    if (!(max_reproj_error > 0.0) || !(success_prob > 0.0 && success_prob < 1.0) || min_iters < 0)
+        return fail(XFH_ERR_ARG, "%s: threshold %g / success_prob %g / min_iters %d", who, max_reproj_error, success_prob, min_iters);
+    if (max_iters < 1 || max_iters > 16384) return fail(XFH_ERR_UNSUPPORTED, "%s: max_iters %d outside [1, 16384]", who, max_iters);
+    int rc = check_ws(workspace, workspace_bytes, xfh::abspose_workspace_bytes(P, max_iters));
+    if (rc) return rc;
+    if (launch_estimate_abspose(pts2d, pts3d, idx2d, idx3d, cap2, cap3, counts, n_const, P, cap, K, max_reproj_error, min_iters, max_iters, success_prob,
+                                seed, R, t, mask, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: unsupported configuration", who);
+    return check_launch(who);
+}
+
+int xfh_estimate_abspose(const float* pts2d, const float* pts3d, const int32_t* counts, int n_const, int P, int cap, const double* K,
+                         double max_reproj_error, int min_iters, int max_iters, double success_prob, uint64_t seed, double* R, double* t,
+                         uint8_t* mask, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    return estimate_abspose_impl("xfh_estimate_abspose", pts2d, pts3d, nullptr, nullptr, cap, cap, counts, n_const, P, cap, K, max_reproj_error,
+                                 min_iters, max_iters, success_prob, seed, R, t, mask, info, workspace, workspace_bytes, stream);
+}
+
+int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* points3d, int cap3d, const int64_t* idx2d, const int64_t* idx3d,
+                                 const int32_t* n_matches, int P, int cap, const double* K, double max_reproj_error, int min_iters,
+                                 int max_iters, double success_prob, uint64_t seed, double* R, double* t, uint8_t* mask, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    if (!idx2d || !idx3d || !n_matches) return fail(XFH_ERR_ARG, "xfh_estimate_abspose_matches: NULL argument");
+    return estimate_abspose_impl("xfh_estimate_abspose_matches", kpts2d, points3d, idx2d, idx3d, cap2d, cap3d, n_matches, 0, P, cap, K,
+                                 max_reproj_error, min_iters, max_iters, success_prob, seed, R, t, mask, info, workspace, workspace_bytes, stream);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

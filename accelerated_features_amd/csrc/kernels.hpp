@@ -112,6 +112,11 @@ int launch_estimate_relpose_sweep(const float* p0, const float* p1, const int64_
                                   int P, int cap, const double* K0, const double* K1, const double* max_errs, int T, int min_iters, int max_iters,
                                   double success_prob, unsigned long long seed, double* R, double* t, double* E, unsigned char* mask, int32_t* info,
                                   void* ws, hipStream_t st);
+// ---- k_abspose.hip (P3P RANSAC + Gauss-Newton refinement: absolute pose from 2D-3D correspondences) ----
+size_t abspose_workspace_bytes(int P, int max_iters);
+int launch_estimate_abspose(const float* p2, const float* p3, const int64_t* idx2, const int64_t* idx3, int cap2, int cap3, const int32_t* counts,
+                            int n_const, int P, int cap, const double* K, double max_err, int min_iters, int max_iters, double success_prob,
+                            unsigned long long seed, double* R, double* t, unsigned char* mask, int32_t* info, void* ws, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

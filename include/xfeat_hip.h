@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define XFH_VERSION 301          /* major*10000 + minor*100 + patch */
+#define XFH_VERSION 302          /* major*10000 + minor*100 + patch */
 
 enum {
     XFH_OK = 0,
@@ -350,6 +350,37 @@ int xfh_estimate_relpose_sweep_matches(const float* kpts0, const float* kpts1, i
                                        const double* max_epipolar_errors, int T, int min_iters, int max_iters, double success_prob,
                                        uint64_t seed, double* R, double* t, double* E, uint8_t* mask, int32_t* info,
                                        void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Absolute pose from 2D-3D correspondences -- localisation against a model, or against a reference image with a depth map:
+ *     pose, info = poselib.estimate_absolute_pose(points2D, points3D, camera, {"max_reproj_error": thr}, {})
+ * for P query images at once.  poselib is not part of the reference tree: the algorithm is the published one (P3P RANSAC on
+ * the classical quartic, MSAC on the reprojection error, Gauss-Newton refinement), specified in DESIGN.md 3.12 /
+ * csrc/k_abspose.hip -- same estimate, not poselib's random stream.
+ *   pts2d (P,cap,2) fp32 pixel coordinates in the query image, pts3d (P,cap,3) fp32 points in any world frame (device), row
+ *   i of one matches row i of the other; pair p uses its first counts[p] rows (device int32; NULL: n_const for all); K
+ *   (P,3,3) fp64 PINHOLE intrinsics of the query camera (device).  max_reproj_error in pixels (converted with (fx + fy) / 2).
+ *   All max_iters (<= 16384; larger is an error) hypotheses are scored on the device, the stopping rule (min_iters,
+ *   success_prob) applied to the cost list afterwards.
+ *   R (P,9) fp64 row-major, t (P,3) fp64 with X_cam = R X_world + t (t in the world's unit, not normalised); mask (P,cap)
+ *   uint8, 1 = reprojection error below the threshold and the point in front of the camera; info (P,8) int32: found,
+ *   winning hypothesis, hypotheses the loop would have run, inliers, accepted refinement steps, n, cost (lo, hi word).
+ *   Fewer than 3 correspondences / inliers: found = 0 and zeros in R, t and the mask.  A correspondence with a coordinate
+ *   that is not finite is never sampled into a model and never an inlier.
+ *   xfh_estimate_abspose_matches: the same on key-points (P,cap2d,2), 3D points (P,cap3d,3) -- the two capacities are
+ *   independent -- and the matcher's lists: correspondence i of pair p is (kpts2d[p][idx2d[p][i]], points3d[p][idx3d[p][i]])
+ *   for i < n_matches[p]; idx (P,cap) int64.
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_abspose_workspace_bytes(int P, int max_iters);
+int xfh_estimate_abspose(const float* pts2d, const float* pts3d, const int32_t* counts, int n_const, int P, int cap,
+                         const double* K, double max_reproj_error, int min_iters, int max_iters, double success_prob,
+                         uint64_t seed, double* R, double* t, uint8_t* mask, int32_t* info,
+                         void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* points3d, int cap3d, const int64_t* idx2d,
+                                 const int64_t* idx3d, const int32_t* n_matches, int P, int cap, const double* K,
+                                 double max_reproj_error, int min_iters, int max_iters, double success_prob, uint64_t seed,
+                                 double* R, double* t, uint8_t* mask, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
