@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("XFH_LIB_PATH") or os.path.join(_HERE, "libxfeat_hip.s
 XFH_OK = 0
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 LG_NO_PRUNING = 1 << 30
+GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY = 0, 1
 SAMPLE_MODES = {'nearest': 0, 'bilinear': 1, 'bicubic': 2}
 PROF_NONE, PROF_CONV_MFMA, PROF_MATCH, PROF_BLOCK1, PROF_HEADS, PROF_CONV_64_64_S1, PROF_CONV_24_24, PROF_CONV_LAYER0 = 0, 1, 2, 3, 4, 5, 6, 100
 PROF_ALL = 1000
@@ -41,6 +42,8 @@ SIGNATURES = {
     "xfh_extract_dense": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "xfh_match_workspace_bytes": (_sz, [_i, _i, _i]),
     "xfh_match_mnn": (_i, [_p, _p, _sz, _p, _sz, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "xfh_match_guided_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_match_mnn_guided": (_i, [_p, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _p, _i, _i, _i, _i, _i, _p, _i, C.c_double, _f, _p, _p, _p, _p, _sz, _p]),
     "xfh_refine_workspace_bytes": (_sz, [_i, _i]),
     "xfh_refine_matches": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "xfh_kpts_heatmap": (_i, [_p, _i, _i, _i, _p, _p]),

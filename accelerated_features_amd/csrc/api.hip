@@ -226,6 +226,18 @@ static size_t carve_match(void* ws, int P, int N1, int N2, MatchWs& o) {
     return align_up(c.off, 256);
 }
 
+static size_t carve_guided(void* ws, int P, int N1, int N2, GuidedWs& o) {
+    Carver c(ws);
+    const size_t z0 = c.off;
+    o.rowkey = c.take<unsigned long long>((size_t)P * N1);
+    o.colkey = c.take<unsigned long long>((size_t)P * N2);
+    o.zeroed = ws ? (char*)ws + z0 : nullptr;
+    o.zeroed_bytes = c.off - z0;
+    o.rowc = c.take<float4>((size_t)P * N1);
+    o.colc = c.take<float4>((size_t)P * N2);
+    return align_up(c.off, 256);
+}
+
 struct RefineWs { int32_t *offs, *total, *rowmap; float *actA, *actB, *rows; unsigned char* keep; };
 static size_t carve_refine(void* ws, int P, int N, RefineWs& o) {
     Carver c(ws);
@@ -776,6 +788,34 @@ int xfh_match_mnn(xfh_handle h, const float* d1, size_t pair_stride1, const floa
     launch_match(w, d1, pair_stride1, d2, pair_stride2, n1, n2, n_stride, n_offset2, P, N1, N2, min_cossim, idx0, idx1,
                  n_matches, (hipStream_t)stream, h ? &h->prof : nullptr, d1_f16, d2_f16, h ? h->opt.match_exact != 0 : false, h ? h->opt.match_sweep : 0);
     return check_launch("xfh_match_mnn");
+}
+
+size_t xfh_match_guided_workspace_bytes(int P, int N1, int N2) {
+    if (P <= 0 || N1 <= 0 || N2 <= 0) return 0;
+    GuidedWs o;
+    return carve_guided(nullptr, P, N1, N2, o);
+}
+
+int xfh_match_mnn_guided(const float* d1, size_t pair_stride1, const float* d2, size_t pair_stride2, const float* kpts1, size_t kpt_stride1,
+                         const float* kpts2, size_t kpt_stride2, const int32_t* n1, const int32_t* n2, int n_stride, int n_offset2, int P, int N1,
+                         int N2, const double* models, int kind, double max_error, float min_cossim, int64_t* idx0, int64_t* idx1,
+                         int32_t* n_matches, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    if (!d1 || !d2 || !kpts1 || !kpts2 || !models || !idx0 || !idx1 || !n_matches) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: NULL argument");
+    if (P <= 0 || N1 <= 0 || N2 <= 0 || P > 65535) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: bad shape");
+    if ((long)P * ((N1 + 1023) / 1024) > 0x7fffffffL / 1024) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: P * N1 too large");
+    if ((long)P * (((N1 > N2 ? N1 : N2) + 255) / 256) > 0x7fffffffL) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: P * max(N1, N2) too large");
+    if (N2 > (1 << 21)) return fail(XFH_ERR_UNSUPPORTED, "xfh_match_mnn_guided: N2 %d beyond 2^21 (the sweep keeps 16-bit tile numbers)", N2);
+    if ((pair_stride1 & 3) || (pair_stride2 & 3)) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: pair strides must be multiples of 4 floats");
+    if (kind != XFH_GUIDE_FUNDAMENTAL && kind != XFH_GUIDE_HOMOGRAPHY)
+        return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: kind %d (XFH_GUIDE_FUNDAMENTAL 0, XFH_GUIDE_HOMOGRAPHY 1)", kind);
+    if (!(max_error > 0.0) || !std::isfinite(max_error)) return fail(XFH_ERR_ARG, "xfh_match_mnn_guided: max_error %g must be positive and finite", max_error);
+    GuidedWs w;
+    const size_t need = carve_guided(workspace, P, N1, N2, w);
+    int rc = check_ws(workspace, workspace_bytes, need);
+    if (rc) return rc;
+    launch_match_guided(w, d1, pair_stride1, d2, pair_stride2, kpts1, kpt_stride1, kpts2, kpt_stride2, n1, n2, n_stride, n_offset2, P, N1, N2, models,
+                        kind, max_error, min_cossim, idx0, idx1, n_matches, (hipStream_t)stream);
+    return check_launch("xfh_match_mnn_guided");
 }
 
 size_t xfh_refine_workspace_bytes(int P, int N) {

@@ -156,7 +156,9 @@ __device__ inline bool mutual_keep(const unsigned long long* __restrict__ rk, co
                                    float min_cossim, int& m) {
     const unsigned long long key = rk[row];                                        // (ord(row max) << 32) | ~arg-max column
     m = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-    if (key == 0ull || (unsigned)m >= (unsigned)n2) { m = 0; return false; }       // no key was ever folded in (non-finite descriptors): no match, no out-of-range read
+    // no key was ever folded in (non-finite descriptors), or the row maximum is -inf (the guided sweep: no element of the row passed its gate; ord(-inf) =
+    // 0x007fffff): no match, no out-of-range read
+    if (key == 0ull || (unsigned)(key >> 32) == 0x007fffffu || (unsigned)m >= (unsigned)n2) { m = 0; return false; }
     const int back = (int)(0xffffffffu - (unsigned)(cb[m] & 0xffffffffu));        // arg-max row of column m
     return (back == row) && (min_cossim <= 0.f || ord_float((unsigned)(key >> 32)) > min_cossim);
 }
@@ -240,11 +242,15 @@ void launch_match(const MatchWs& ws, const float* d1, size_t ps1, const float* d
         prof_end(prof, XFH_SPAN_MATCH_EXACT, st, 0, 0);
     }
     prof_end(prof, XFH_PROF_MATCH, st, 2.0 * P * (double)N1 * N2 * 64, (double)P * (N1 + N2) * 64 * 4);
-    const int chunks = ceil_div(N1, 1024);
     prof_begin(prof, XFH_SPAN_MATCH_FINALIZE, st);
-    mnn_finalize_kernel<<<P * chunks, 1024, 0, st>>>(n1, n2, n_stride, n_off2, N1, N2, chunks, ws.rowkey, ws.colkey,
-                                                     min_cossim, idx0, idx1, n_matches);
+    launch_match_finalize(ws.rowkey, ws.colkey, n1, n2, n_stride, n_off2, P, N1, N2, min_cossim, idx0, idx1, n_matches, st);
     prof_end(prof, XFH_SPAN_MATCH_FINALIZE, st, 0, 0);
+}
+
+void launch_match_finalize(const unsigned long long* rowkey, const unsigned long long* colkey, const int32_t* n1, const int32_t* n2, int n_stride, int n_off2,
+                           int P, int N1, int N2, float min_cossim, int64_t* idx0, int64_t* idx1, int32_t* n_matches, hipStream_t st) {
+    const int chunks = ceil_div(N1, 1024);
+    mnn_finalize_kernel<<<P * chunks, 1024, 0, st>>>(n1, n2, n_stride, n_off2, N1, N2, chunks, rowkey, colkey, min_cossim, idx0, idx1, n_matches);
 }
 
 }  // namespace xfh

@@ -203,6 +203,22 @@ void launch_match(const MatchWs& ws, const float* d1, size_t ps1, const float* d
                   bool exact_only = false, int sweep_form = 0);
 int match_row_blocks(int N1);
 int match_debug_occupancy();
+// the mutual test + ordered compaction over (rowkey, colkey): the tail of launch_match, shared with the guided matcher
+void launch_match_finalize(const unsigned long long* rowkey, const unsigned long long* colkey, const int32_t* n1, const int32_t* n2, int n_stride, int n_off2,
+                           int P, int N1, int N2, float min_cossim, int64_t* idx0, int64_t* idx1, int32_t* n_matches, hipStream_t st);
+
+// ---- k_match_guided.hip (mutual nearest neighbours gated by a two-view model: the exact sweep of k_match.hip with a geometric test in its epilogue) ----
+struct GuidedWs {
+    void* zeroed; size_t zeroed_bytes;      // [rowkey | colkey], one memset per call
+    unsigned long long* rowkey;    // (P,N1), (P,N2): the key layout of MatchWs, read by the same finalize
+    unsigned long long* colkey;
+    float4* rowc;                  // (P,N1) per-row gate constants: F (l0, l1, l2, thr^2 rho) / H (U, V, -, -); NaN = the row passes nothing
+    float4* colc;                  // (P,N2) per-column constants: (x, y, thr^2 gamma (F) / thr^2 (H), -)
+};
+// kind 0: fundamental (Sampson), 1: homography (forward transfer); models (P,9) fp64 device
+void launch_match_guided(const GuidedWs& ws, const float* d1, size_t ps1, const float* d2, size_t ps2, const float* k1, size_t ks1, const float* k2, size_t ks2,
+                         const int32_t* n1, const int32_t* n2, int n_stride, int n_off2, int P, int N1, int N2, const double* models, int kind, double thr,
+                         float min_cossim, int64_t* idx0, int64_t* idx1, int32_t* n_matches, hipStream_t st);
 
 // ---- k_refine.hip -----------------------------------------------------------------------
 void launch_refine_rowmap(const int32_t* n_matches, int P, int N, int32_t* offs, int32_t* rowmap, int32_t* total,

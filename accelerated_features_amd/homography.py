@@ -83,18 +83,27 @@ class ReferenceTracker:
     """The XFeat branch of the reference demo's per-frame work (realtime_demo.py:136-142 and 204-231) for B camera streams at once, with
     everything resident in HBM: reference features are extracted once and cached (``ref_precomp``), every new frame goes through
     detectAndCompute -> mutual-NN match against the cached descriptors (``min_cossim`` 0.82) -> MAGSAC++ homography
-    (``ransac_thr``, maxIters 700, confidence 0.995); a homography with fewer than ``min_inliers`` inliers is dropped (``self.H = None``)."""
+    (``ransac_thr``, maxIters 700, confidence 0.995); a homography with fewer than ``min_inliers`` inliers is dropped (``self.H = None``).
 
-    def __init__(self, xfeat, top_k=4096, min_cossim=0.82, ransac_thr=4.0, min_inliers=50, max_iters=700, confidence=0.995, seed=0):
+    ``guided=True``: a stream whose last step found an H is matched again among the candidates that H allows (guided.match_guided_device,
+    forward transfer error <= ``guide_thr`` pixels: the motion between two frames plus the estimate's own error) and keeps that result when
+    its homography has at least ``min_inliers`` inliers; a stream without an H, or whose guided inliers drop below ``min_inliers``, keeps
+    the plain matcher's result of the same step.  Both run on the device, the choice is made there.  The default (False) is the plain path alone."""
+
+    def __init__(self, xfeat, top_k=4096, min_cossim=0.82, ransac_thr=4.0, min_inliers=50, max_iters=700, confidence=0.995, seed=0, guided=False,
+                 guide_thr=16.0):
         self.xfeat, self.top_k, self.min_cossim = xfeat, top_k, min_cossim
         self.ransac_thr, self.min_inliers, self.max_iters, self.confidence, self.seed = ransac_thr, min_inliers, max_iters, confidence, seed
+        self.guided, self.guide_thr = guided, guide_thr
         self.ref = None
+        self.last_H = None                     # guided: (B,3,3) float64, the H of the last step, zero for a stream without one
 
     def set_reference(self, frames):
         """frames (B,C,H,W) (or (B,H,W,C) uint8 like the demo's camera frames): cache their key-points and descriptors."""
         kp, sc, de, nv, nc, cap, hw = self.xfeat._detect_device(self.xfeat.parse_input(frames), self.top_k)
         self.ref = (kp, de, nv.clone())
         self.ref_overflow = (nc, cap)          # device counts: see `overflowed`
+        self.last_H = None
 
     def track(self, frames):
         """One step for the B current frames.  Returns CUDA tensors: 'H' (B,3,3) float64, 'valid' (B,) bool (inliers >= min_inliers),
@@ -108,9 +117,30 @@ class ReferenceTracker:
             raise RuntimeError('the current frames must have the batch size of the reference frames')
         idx0, idx1, n = self.xfeat.match_sets_device(de0, nv0, de1, nv1, self.min_cossim)
         r = find_homography_matches(kp0, kp1, idx0, idx1, n, self.ransac_thr, self.max_iters, self.confidence, self.seed)
+        if self.guided:
+            idx0, idx1, n = self._guided_step(r, kp0, de0, nv0, kp1, de1, nv1, idx0, idx1, n)
         r.update(valid=(r['info'][:, 0] > 0) & (r['info'][:, 3] >= self.min_inliers), idx0=idx0, idx1=idx1, n_matches=n, keypoints=kp1,
                  n_candidates=nc, nms_capacity=cap, fx_status=self.xfeat.net._status_target)      # fx_status: see `range_exceeded`
         return r
+
+    def _guided_step(self, r, kp0, de0, nv0, kp1, de1, nv1, idx0, idx1, n):
+        """The guided half of track(): replaces, stream by stream, the plain result `r` and its match lists by the guided ones where those hold,
+        and remembers the step's H for the next one."""
+        from .guided import match_guided_device
+        if self.last_H is not None:
+            g0, g1, gn = match_guided_device(de0, kp0, nv0, de1, kp1, nv1, self.last_H, 'homography', self.guide_thr, self.min_cossim)
+            rg = find_homography_matches(kp0, kp1, g0, g1, gn, self.ransac_thr, self.max_iters, self.confidence, self.seed)
+            use = (rg['info'][:, 0] > 0) & (rg['info'][:, 3] >= self.min_inliers)
+            r['H'] = torch.where(use[:, None, None], rg['H'], r['H'])
+            r['inliers'] = torch.where(use[:, None], rg['inliers'], r['inliers'])
+            r['info'] = torch.where(use[:, None], rg['info'], r['info'])
+            idx0, idx1, n = torch.where(use[:, None], g0, idx0), torch.where(use[:, None], g1, idx1), torch.where(use, gn, n)
+            r['guided'] = use
+        else:
+            r['guided'] = torch.zeros_like(n, dtype=torch.bool)
+        ok = (r['info'][:, 0] > 0) & (r['info'][:, 3] >= self.min_inliers)
+        self.last_H = torch.where(ok[:, None, None], r['H'], torch.zeros_like(r['H']))
+        return idx0, idx1, n
 
     def range_exceeded(self, fx_status):
         """True if an activation left the range of the fp16-pair arithmetic since the last check (device int32 `fx_status` of track()'s result, non-zero; never seen on

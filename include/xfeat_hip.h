@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define XFH_VERSION 302          /* major*10000 + minor*100 + patch */
+#define XFH_VERSION 303          /* major*10000 + minor*100 + patch */
 
 enum {
     XFH_OK = 0,
@@ -236,6 +236,45 @@ int xfh_match_mnn(xfh_handle h /* may be NULL */, const float* d1, size_t pair_s
                   int P, int N1, int N2, float min_cossim,
                   int64_t* idx0, int64_t* idx1, int32_t* n_matches,
                   void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Guided matching: mutual nearest neighbours among the candidates that agree with a known two-view model (a fundamental
+ * matrix, an essential matrix brought to pixels, a homography) -- the arg-max of xfh_match_mnn taken again under the geometry
+ * the estimators below found.  Element (i, j) takes part in row i's and in column j's arg-max only if key-point i of image 0
+ * and key-point j of image 1 pass the gate; every similarity is an fp32 dot product on the f32 matrix cores (the exact kernel
+ * of xfh_match_mnn, csrc/k_match.hip, with the gate in its epilogue: csrc/k_match_guided.hip, no fp16 filter).
+ *
+ *   d1/d2, pair strides, n1/n2, n_stride, n_offset2, min_cossim, idx0/idx1/n_matches: as for xfh_match_mnn
+ *   kpts1/kpts2: (x,y) fp32 pixel coordinates of the rows of d1 / d2; pair p at kpts + p*kpt_stride (strides in floats)
+ *   models: P x 9 fp64 row-major (device), one model M per pair; max_error: the gate's threshold thr in pixels
+ *
+ *   kind XFH_GUIDE_FUNDAMENTAL (model M with x1' M x0 = 0, the convention of xfh_find_fundamental; for E pass
+ *   F = K1^-T E K0^-1): the Sampson error, the quantity xfh_find_fundamental thresholds, without its division.
+ *   Element (i, j) passes iff
+ *       e^2 <= thr^2 * (rho_i + gamma_j)
+ *   with l = M (x0_i, 1), rho_i = l0^2 + l1^2, m = M' (x1_j, 1), gamma_j = m0^2 + m1^2, e = (l0 x1_j.x + l1 x1_j.y) + l2.
+ *   The per-row constants (l, rho) and the per-column constant (gamma) are computed once in fp64 from the fp64 model (scaled
+ *   by 1 / max |M_ab| first: the gate does not depend on the model's scale) and rounded to fp32, thr^2 folded into rho and
+ *   gamma before the rounding; only e, the sum and the compare run per element, in fp32.
+ *
+ *   kind XFH_GUIDE_HOMOGRAPHY (forward transfer error, as cv2.findHomography thresholds it):
+ *   (U,V) = dehom(H (x0_i, 1)), computed once per row in fp64 and rounded to fp32.  Element (i, j) passes iff
+ *       (U - x1_j.x)^2 + (V - x1_j.y)^2 <= thr^2.
+ *   A row whose homogeneous w is non-finite or |w| <= DBL_EPSILON * |row 3 of H| passes nothing.
+ *
+ *   A row or column without a passing element has no match.  An all-zero model (what the estimators write where nothing was
+ *   found) and a model with a non-finite entry give no matches for their pair.  max_error <= 0 or non-finite: XFH_ERR_ARG.
+ *   N2 <= 2^21 (XFH_ERR_UNSUPPORTED beyond).
+ * outputs: idx0, idx1 (P,N1) int64 (idx0 ascending), n_matches (P) int32; ties resolve to the lowest index.
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_GUIDE_FUNDAMENTAL 0
+#define XFH_GUIDE_HOMOGRAPHY  1
+size_t xfh_match_guided_workspace_bytes(int P, int N1, int N2);
+int xfh_match_mnn_guided(const float* d1, size_t pair_stride1, const float* d2, size_t pair_stride2,
+                         const float* kpts1, size_t kpt_stride1, const float* kpts2, size_t kpt_stride2,   /* (x,y) fp32, strides in floats */
+                         const int32_t* n1, const int32_t* n2, int n_stride, int n_offset2, int P, int N1, int N2,
+                         const double* models /* P x 9 row-major, device */, int kind, double max_error, float min_cossim,
+                         int64_t* idx0, int64_t* idx1, int32_t* n_matches, void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Match refinement.  Replaces XFeat.refine_matches (modules/xfeat.py:306-325),
