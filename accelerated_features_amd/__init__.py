@@ -3,3 +3,5 @@
     from accelerated_features_amd import XFeat      # drop-in for modules.xfeat.XFeat
 """
 from .xfeat import XFeat, XFeatModel  # noqa: F401
+from .structure import (essential_from_fundamental, recover_pose, recover_pose_batch, recover_pose_matches,  # noqa: F401
+                        triangulate_batch, triangulate_matches)

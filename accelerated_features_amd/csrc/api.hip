@@ -1040,6 +1040,78 @@ int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* po
                                  max_reproj_error, min_iters, max_iters, success_prob, seed, R, t, mask, info, workspace, workspace_bytes, stream);
 }
 
+// ---- two-view structure (k_triangulate.hip): no workspace; every check returns before any launch
+static int structure_shape_check(const char* who, const float* pts0, const float* pts1, const double* K0, const double* K1, const int32_t* counts,
+                                 int n_const, int P, int cap, int kcap) {
+    if (!pts0 || !pts1 || !K0 || !K1) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (P < 1 || P > 65535) return fail(XFH_ERR_ARG, "%s: P %d outside [1, 65535]", who, P);
+    if (cap < 1 || cap > (1 << 24) || kcap < 1 || (!counts && (n_const < 0 || n_const > cap)))
+        return fail(XFH_ERR_ARG, "%s: bad shape (cap %d, key-point capacity %d, n %d)", who, cap, kcap, n_const);
+    return XFH_OK;
+}
+
+static int triangulate_impl(const char* who, const float* pts0, const float* pts1, const int64_t* idx0, const int64_t* idx1, int kcap,
+                            const int32_t* counts, int n_const, int P, int cap, const double* K0, const double* K1, const double* R, const double* t,
+                            const uint8_t* mask, double max_reproj_error, double cos_min, double max_depth, float* points3d, uint8_t* status,
+                            float* reproj_error, int32_t* info, float* points3d_ref, xfh_stream stream) {
+    if (!R || !t || !points3d || !status || !reproj_error || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    int rc = structure_shape_check(who, pts0, pts1, K0, K1, counts, n_const, P, cap, kcap);
+    if (rc) return rc;
+    if (!(max_reproj_error > 0.0) || !std::isfinite(max_reproj_error))
+        return fail(XFH_ERR_ARG, "%s: max_reproj_error %g must be positive and finite", who, max_reproj_error);
+    if (!(max_depth > 0.0)) return fail(XFH_ERR_ARG, "%s: max_depth %g must be positive (+inf: no limit)", who, max_depth);
+    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return fail(XFH_ERR_ARG, "%s: cos_min %g outside [-1, 1]", who, cos_min);
+    if (launch_triangulate(pts0, pts1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, R, t, mask, max_reproj_error, cos_min, max_depth, points3d,
+                           status, reproj_error, info, points3d_ref, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
+int xfh_triangulate(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap, const double* K0, const double* K1,
+                    const double* R, const double* t, const uint8_t* mask, double max_reproj_error, double cos_min, double max_depth,
+                    float* points3d, uint8_t* status, float* reproj_error, int32_t* info, xfh_stream stream) {
+    return triangulate_impl("xfh_triangulate", pts0, pts1, nullptr, nullptr, cap, counts, n_const, P, cap, K0, K1, R, t, mask, max_reproj_error,
+                            cos_min, max_depth, points3d, status, reproj_error, info, nullptr, stream);
+}
+
+int xfh_triangulate_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1, const int32_t* n_matches,
+                            int P, int cap, const double* K0, const double* K1, const double* R, const double* t, const uint8_t* mask,
+                            double max_reproj_error, double cos_min, double max_depth, float* points3d, uint8_t* status, float* reproj_error,
+                            int32_t* info, float* points3d_ref, xfh_stream stream) {
+    if (!idx0 || !idx1 || !n_matches) return fail(XFH_ERR_ARG, "xfh_triangulate_matches: NULL argument");
+    return triangulate_impl("xfh_triangulate_matches", kpts0, kpts1, idx0, idx1, kpt_cap, n_matches, 0, P, cap, K0, K1, R, t, mask,
+                            max_reproj_error, cos_min, max_depth, points3d, status, reproj_error, info, points3d_ref, stream);
+}
+
+static int recover_pose_impl(const char* who, const float* pts0, const float* pts1, const int64_t* idx0, const int64_t* idx1, int kcap,
+                             const int32_t* counts, int n_const, int P, int cap, const double* K0, const double* K1, const double* E,
+                             const uint8_t* mask_in, double distance_thresh, double* R, double* t, int32_t* good, uint8_t* mask, float* points3d,
+                             int32_t* info, xfh_stream stream) {
+    if (!E || !R || !t || !good || !mask || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    int rc = structure_shape_check(who, pts0, pts1, K0, K1, counts, n_const, P, cap, kcap);
+    if (rc) return rc;
+    if (!(distance_thresh > 0.0)) return fail(XFH_ERR_ARG, "%s: distance_thresh %g must be positive (+inf: no limit)", who, distance_thresh);
+    if (launch_recover_pose(pts0, pts1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, E, mask_in, distance_thresh, R, t, good, mask, points3d,
+                            info, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
+int xfh_recover_pose(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap, const double* K0, const double* K1,
+                     const double* E, const uint8_t* mask_in, double distance_thresh, double* R, double* t, int32_t* good, uint8_t* mask,
+                     float* points3d, int32_t* info, xfh_stream stream) {
+    return recover_pose_impl("xfh_recover_pose", pts0, pts1, nullptr, nullptr, cap, counts, n_const, P, cap, K0, K1, E, mask_in, distance_thresh, R, t,
+                             good, mask, points3d, info, stream);
+}
+
+int xfh_recover_pose_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1, const int32_t* n_matches,
+                             int P, int cap, const double* K0, const double* K1, const double* E, const uint8_t* mask_in, double distance_thresh,
+                             double* R, double* t, int32_t* good, uint8_t* mask, float* points3d, int32_t* info, xfh_stream stream) {
+    if (!idx0 || !idx1 || !n_matches) return fail(XFH_ERR_ARG, "xfh_recover_pose_matches: NULL argument");
+    return recover_pose_impl("xfh_recover_pose_matches", kpts0, kpts1, idx0, idx1, kpt_cap, n_matches, 0, P, cap, K0, K1, E, mask_in, distance_thresh,
+                             R, t, good, mask, points3d, info, stream);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

@@ -1,0 +1,446 @@
+// Two-view structure: the 3D points that the correspondences of a pair see under a relative pose (triangulation), and the pose of an
+// essential matrix chosen by those points (what cv2.recoverPose does for modules/eval/scannet1500.py:84 of the reference: decompose E into
+// four poses, keep the one that puts the points in front of both cameras).  cv2 is not available offline, so nothing here is pinned to it:
+// what is implemented is the published method -- Lindstrom's optimal two-view correction ("Triangulation made easy", CVPR 2010, variant
+// niter2 with its closing step solved exactly) followed by the closed-form depths of the corrected rays.  The specification (tests/structure_reference.py is a
+// numpy restatement of it, operation for operation, and tests/test_structure_emulated.py compiles the solver below on the host and holds
+// it to that restatement bit for bit):
+//   * inputs of pair p: two point lists (cap rows of 2 fp32 pixels) or, with index lists, two key-point lists (kcap rows) and correspondence
+//     i = (row idx0[i] of image 0, row idx1[i] of image 1); an index outside [0, kcap) makes the correspondence "not finite"; PINHOLE
+//     intrinsics K0, K1 (row-major 3x3); a pose with X1 = R X0 + t and E = [t]x R (tg_pose_E: the formula of k_relpose.hip's rp_pose_E);
+//   * calibration: x0 = ((u0 - cx0) / fx0, (v0 - cy0) / fy0, 1), x1 likewise with K1, in fp64;
+//   * correction onto x1' E x0 = 0 (tg_correct).  With S = [[1,0,0],[0,1,0]] and Et = S E S':
+//         n = S E x0, n' = S E' x1, a = n . (Et n'), b = (n.n + n'.n') / 2, c = x1' E x0, d = sqrt(b^2 - a c),
+//         lambda = c / (b + d), D1 = lambda n, D0 = lambda n', n1 = n - Et D0, n1' = n' - Et' D1 (the gradients at the corrected pair),
+//         then the second step along them: a1 = n1 . (Et n1'), b1 = (n1.n + n1'.n') / 2, lambda1 = c / (b1 + sqrt(b1^2 - a1 c)),
+//         y1 = x1 - lambda1 n1, y0 = x0 - lambda1 n1'  (third components stay 1).
+//     lambda1 is the root of the constraint along (n1', n1), a1 l^2 - 2 b1 l + c = 0, so the pair meets the constraint to rounding; niter2
+//     closes with the approximation lambda 2 d / (n1.n1 + n1'.n1') of that root instead, which leaves up to 1.4e-2 px of epipolar
+//     distance for pairs near an epipole at 10 px of noise; the directions, and with them the optimality, are niter2's.
+//     The displacement does not depend on the scale or sign of E in exact arithmetic and not on its sign in floating point;
+//   * depths (tg_depths): r = R y0, z = y1 x r, zz = z.z, l0 = -(z . (y1 x t)) / zz, l1 = (z . (t x r)) / zz, X = l0 y0 in camera 0's frame
+//     and the unit of t; l0 and l1 are the z-depths in the two cameras;
+//   * status, the first failing gate wins: 0 valid; 1 masked out by the input mask (rows at or beyond the pair's count are written as 1
+//     too and are not counted in info); 2 not finite (a coordinate that is not finite, an index out of range, an unusable pose = an entry
+//     that is not finite, R all zero, t all zero; zz not > 0; X or l1 not finite); 3 behind (l0 <= 0 or l1 <= 0); 4 far (l0 or l1 >
+//     max_depth); 5 reprojection (max(e0^2, e1^2) > max_reproj_error^2, e0^2 = ((y0.x - x0.x) fx0)^2 + ((y0.y - x0.y) fy0)^2, e1^2 alike);
+//     6 parallax (cos = (r.y1) / sqrt((r.r)(y1.y1)) > cos_min; the host passes cos_min = cos(min_parallax_deg): no trigonometry here);
+//   * outputs per correspondence: X as 3 fp32, NaN unless the status is 0 (the convention of unproject_keypoints); the status; the
+//     reprojection error sqrt(max(e0^2, e1^2)) as fp32, NaN for status 1 and 2;
+//   * pose from E (tg_decompose): E at any scale or sign; s^2 = tr(E E') / 2, t = the cross product of two columns of E (largest norm)
+//     made unit, R = cof(E) / s^2 -+ [t]x E / s, the poses in the order (Ra, t) (Ra, -t) (Rb, t) (Rb, -t) -- the decomposition inside
+//     relpose_solve of k_relpose.hip, restated here (a DUPLICATE: that one works on the LDS slice of a hypothesis and its emulated tests
+//     hold it bit for bit, so it is left alone), each R then moved to the nearest rotation by three Newton-Schulz steps (tg_orthonormalise:
+//     the result is the SVD decomposition's rotation when E = K1' F K0 is essential only nearly).  E with an entry that is not finite, s^2 or the cross product not > 0, or a pose that is
+//     not finite: unusable.  The correction runs once on E / s and the four depth solves reuse it; pose q gets the vote of every
+//     correspondence that passes gates 1-4 under it with max_depth = distance_thresh (cv2.recoverPose's: depth in (0, distance_thresh) in
+//     both cameras); the winner is the highest count, ties to the lowest pose index; an unusable E or a best count of 0: found = 0, zeros;
+//   * only + - * / sqrt in all of it, every product and sum rounded once (fp contraction off in this file).
+//
+// Launches per call (no workspace):
+//   triangulate_kernel   : thread = correspondence, grid = (chunks of 256 of cap, P); the pair's pose and intrinsics through LDS once per
+//                          workgroup; per-pair status counts by wave ballots + popcount, one integer atomic per wave and status (integer
+//                          sums carry no order: info is reproducible); optional scatter of the valid points to image 0's key-point rows
+//   recover_pose_kernel  : one workgroup per pair: decomposition, the four votes (integer LDS atomics), the winner, its mask and points
+#include "ransac_common.hpp"
+#include "twoview_math.hpp"
+
+#pragma clang fp contract(off)
+
+namespace xfh {
+
+// ---- solver begin (host-compilable: tests/test_structure_emulated.py slices it out behind the slice of twoview_math.hpp and drops the
+// __device__ qualifiers) ----
+namespace tg {
+constexpr int VALID = 0, MASKED = 1, NOT_FINITE = 2, BEHIND = 3, FAR = 4, REPROJ = 5, PARALLAX = 6, NSTATUS = 7;
+constexpr int POLAR_STEPS = 3;              // tg_orthonormalise
+}  // namespace tg
+
+// E = [t]x R
+__device__ inline void tg_pose_E(const double* R, const double* t, double* E) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        E[j] = t[1] * R[6 + j] - t[2] * R[3 + j];
+        E[3 + j] = t[2] * R[j] - t[0] * R[6 + j];
+        E[6 + j] = t[0] * R[3 + j] - t[1] * R[j];
+    }
+}
+// a pose that can triangulate: every entry finite, R not all zero (what "not found" pairs carry), t not zero
+__device__ inline bool tg_pose_ok(const double* R, const double* t) {
+    bool fin = true, rnz = false, tnz = false;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { fin = fin && tv::is_finite(R[k]); rnz = rnz || R[k] != 0.0; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { fin = fin && tv::is_finite(t[k]); tnz = tnz || t[k] != 0.0; }
+    return fin && rnz && tnz;
+}
+// a correspondence after calibration and correction: y0, y1 the corrected rays (third component 1), e2 = max(e0^2, e1^2) in pixels^2
+struct TgRays {
+    double y0x, y0y, y1x, y1y, e2;
+    bool fin;                                              // the four pixel coordinates are finite
+};
+// cal = fx0 fy0 cx0 cy0 fx1 fy1 cx1 cy1
+__device__ inline TgRays tg_correct(const double* E, const double* cal, double u0, double v0, double u1, double v1) {
+    TgRays q;
+    q.fin = tv::is_finite(u0) && tv::is_finite(v0) && tv::is_finite(u1) && tv::is_finite(v1);
+    const double x0x = (u0 - cal[2]) / cal[0], x0y = (v0 - cal[3]) / cal[1];
+    const double x1x = (u1 - cal[6]) / cal[4], x1y = (v1 - cal[7]) / cal[5];
+    double n0 = (E[0] * x0x + E[1] * x0y) + E[2], n1 = (E[3] * x0x + E[4] * x0y) + E[5];            // n  = S E x0
+    double m0 = (E[0] * x1x + E[3] * x1y) + E[6], m1 = (E[1] * x1x + E[4] * x1y) + E[7];            // n' = S E' x1
+    const double a = n0 * (E[0] * m0 + E[1] * m1) + n1 * (E[3] * m0 + E[4] * m1);
+    const double b = 0.5 * ((n0 * n0 + n1 * n1) + (m0 * m0 + m1 * m1));
+    const double c = (x1x * n0 + x1y * n1) + ((E[6] * x0x + E[7] * x0y) + E[8]);
+    const double d = sqrt(b * b - a * c);
+    double lam = c / (b + d);
+    const double d1x = lam * n0, d1y = lam * n1, d0x = lam * m0, d0y = lam * m1;
+    const double p0 = n0, p1 = n1, q0 = m0, q1 = m1;     // the gradients at the measured pair
+    n0 = n0 - (E[0] * d0x + E[1] * d0y); n1 = n1 - (E[3] * d0x + E[4] * d0y);
+    m0 = m0 - (E[0] * d1x + E[3] * d1y); m1 = m1 - (E[1] * d1x + E[4] * d1y);
+    const double a1 = n0 * (E[0] * m0 + E[1] * m1) + n1 * (E[3] * m0 + E[4] * m1);
+    const double b1 = 0.5 * ((n0 * p0 + n1 * p1) + (m0 * q0 + m1 * q1));
+    lam = c / (b1 + sqrt(b1 * b1 - a1 * c));
+    q.y1x = x1x - lam * n0; q.y1y = x1y - lam * n1;
+    q.y0x = x0x - lam * m0; q.y0y = x0y - lam * m1;
+    const double ax = (q.y0x - x0x) * cal[0], ay = (q.y0y - x0y) * cal[1];
+    const double bx = (q.y1x - x1x) * cal[4], by = (q.y1y - x1y) * cal[5];
+    const double e0 = ax * ax + ay * ay, e1 = bx * bx + by * by;
+    q.e2 = e0 > e1 ? e0 : e1;
+    return q;
+}
+// depths l0, l1 of the corrected rays under (R, t), zz = |y1 x R y0|^2 and r = R y0
+__device__ inline void tg_depths(const double* R, const double* t, const TgRays& q, double& l0, double& l1, double& zz, double* r) {
+    const double y1[3] = {q.y1x, q.y1y, 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] = (R[3 * i] * q.y0x + R[3 * i + 1] * q.y0y) + R[3 * i + 2];
+    double z[3], a[3], b[3];
+    tv::cross3(y1, r, z); tv::cross3(y1, t, a); tv::cross3(t, r, b);
+    zz = tv::dot3(z, z);
+    l0 = -tv::dot3(z, a) / zz;
+    l1 = tv::dot3(z, b) / zz;
+}
+// gates 2-4 (what the pose vote shares with the triangulation); X = l0 y0
+__device__ inline int tg_depth_status(bool usable, const TgRays& q, double l0, double l1, double zz, double max_depth, double* X) {
+    X[0] = l0 * q.y0x; X[1] = l0 * q.y0y; X[2] = l0;
+    const bool fin = usable && q.fin && zz > 0.0 && tv::is_finite(X[0]) && tv::is_finite(X[1]) && tv::is_finite(X[2]) && tv::is_finite(l1);
+    if (!fin) return tg::NOT_FINITE;
+    if (!(l0 > 0.0) || !(l1 > 0.0)) return tg::BEHIND;
+    if (l0 > max_depth || l1 > max_depth) return tg::FAR;
+    return tg::VALID;
+}
+// the per-correspondence function: status, X3 (NaN unless valid), err (NaN when masked or not finite); gate = l0, l1, e2, cos for the tests
+__device__ inline int tg_point(const double* R, const double* t, const double* E, bool usable, const double* cal, double u0, double v0, double u1,
+                               double v1, bool masked, double thr2, double cos_min, double max_depth, float* X3, float& err, double* gate) {
+    const TgRays q = tg_correct(E, cal, u0, v0, u1, v1);
+    double l0, l1, zz, r[3], X[3];
+    tg_depths(R, t, q, l0, l1, zz, r);
+    int st = tg_depth_status(usable, q, l0, l1, zz, max_depth, X);
+    const double y1[3] = {q.y1x, q.y1y, 1.0};
+    const double cosv = tv::dot3(r, y1) / sqrt(tv::dot3(r, r) * tv::dot3(y1, y1));
+    if (st == tg::VALID && q.e2 > thr2) st = tg::REPROJ;
+    if (st == tg::VALID && cosv > cos_min) st = tg::PARALLAX;
+    if (masked) st = tg::MASKED;
+    const float nanv = __builtin_nanf("");
+    const bool ok = st == tg::VALID;
+    X3[0] = ok ? (float)X[0] : nanv; X3[1] = ok ? (float)X[1] : nanv; X3[2] = ok ? (float)X[2] : nanv;
+    err = st == tg::MASKED || st == tg::NOT_FINITE ? nanv : (float)sqrt(q.e2);
+    gate[0] = l0; gate[1] = l1; gate[2] = q.e2; gate[3] = cosv;
+    return st;
+}
+// The rotation nearest to R (its polar factor) by tg::POLAR_STEPS Newton-Schulz steps R <- R (3 I - R'R) / 2: for an E that is essential
+// only nearly (K1' F K0 of an estimated F: two singular values that differ) cof(E) / s^2 -+ [t]x E / s is U W diag(s1/s, s2/s, s1 s2/s^2) V',
+// a rotation times a symmetric factor near I, and its polar factor U W V' is the rotation of the SVD decomposition (each step squares the
+// distance from orthonormal: 1e-2 -> 1e-4 -> 1e-8 -> 1e-16); an essential E's R moves in its last bits only
+__device__ inline void tg_orthonormalise(double* R) {
+    for (int it = 0; it < tg::POLAR_STEPS; ++it) {
+        double M[9], Rn[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) M[3 * i + j] = (i == j ? 1.5 : 0.0) - 0.5 * ((R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rn[3 * r + j] = (R[3 * r] * M[j] + R[3 * r + 1] * M[3 + j]) + R[3 * r + 2] * M[6 + j];
+#pragma unroll
+        for (int m = 0; m < 9; ++m) R[m] = Rn[m];
+    }
+}
+// The four poses of E at any scale or sign: Ra, Rb, t (unit) -- (Ra, t) (Ra, -t) (Rb, t) (Rb, -t) -- and En = E / s; false: unusable.
+// (The decomposition of k_relpose.hip's relpose_solve, restated.)
+__device__ inline bool tg_decompose(const double* E, double* Ra, double* Rb, double* t, double* En) {
+    bool ok = true;
+    double s2 = 0.0;
+#pragma unroll
+    for (int m = 0; m < 9; ++m) { ok = ok && tv::is_finite(E[m]); s2 = s2 + E[m] * E[m]; }
+    s2 = s2 * 0.5;
+    double c01[3], c02[3], c12[3];
+    const double k0[3] = {E[0], E[3], E[6]}, k1[3] = {E[1], E[4], E[7]}, k2[3] = {E[2], E[5], E[8]};     // columns: t' E = 0
+    tv::cross3(k0, k1, c01); tv::cross3(k0, k2, c02); tv::cross3(k1, k2, c12);
+    const double n01 = tv::dot3(c01, c01), n02 = tv::dot3(c02, c02), n12 = tv::dot3(c12, c12);
+    const int tp = n12 > (n02 > n01 ? n02 : n01) ? 2 : (n02 > n01 ? 1 : 0);
+    const double nt = tp == 0 ? n01 : (tp == 1 ? n02 : n12);
+    double tc[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) tc[m] = tp == 0 ? c01[m] : (tp == 1 ? c02[m] : c12[m]);
+    ok = ok && nt > 0.0 && s2 > 0.0;
+    const double tn = sqrt(nt), sc = sqrt(s2);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) t[m] = tc[m] / tn;
+    double cof[9], te[9];
+    tv::cross3(E + 3, E + 6, cof); tv::cross3(E + 6, E, cof + 3); tv::cross3(E, E + 3, cof + 6);
+    tg_pose_E(E, t, te);                                   // [t]x E (the same products as [t]x R)
+#pragma unroll
+    for (int m = 0; m < 9; ++m) {
+        const double a = cof[m] / s2, b = te[m] / sc;
+        Ra[m] = a - b; Rb[m] = a + b;
+        En[m] = E[m] / sc;
+    }
+    tg_orthonormalise(Ra);
+    tg_orthonormalise(Rb);
+#pragma unroll
+    for (int m = 0; m < 9; ++m) ok = ok && tv::is_finite(Ra[m]) && tv::is_finite(Rb[m]) && tv::is_finite(En[m]);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) ok = ok && tv::is_finite(t[m]);
+    return ok;
+}
+// status of gates 2-4 of one corrected correspondence under pose Q of the four (compile time: no pose is indexed at run time); X under it
+template <int Q>
+__device__ inline int tg_vote(const double* Ra, const double* Rb, const double* t, bool usable, const TgRays& q, double max_depth, double* X) {
+    const double sg = (Q & 1) ? -1.0 : 1.0;
+    const double tq[3] = {sg * t[0], sg * t[1], sg * t[2]};
+    double l0, l1, zz, r[3];
+    tg_depths(Q < 2 ? Ra : Rb, tq, q, l0, l1, zz, r);
+    return tg_depth_status(usable, q, l0, l1, zz, max_depth, X);
+}
+// the winner of the four counts: the highest, ties to the lowest pose index
+__device__ inline int tg_winner(int c0, int c1, int c2, int c3) {
+    int w = 0, best = c0;
+    if (c1 > best) { w = 1; best = c1; }
+    if (c2 > best) { w = 2; best = c2; }
+    if (c3 > best) { w = 3; best = c3; }
+    return w;
+}
+// ---- solver end ----
+
+struct TgArgs {
+    const float* p0;          // (P, kcap, 2): the correspondences (idx0 == NULL, kcap == cap) or the key-point lists they index
+    const float* p1;
+    const int64_t* idx0;      // (P, cap) rows of p0 / p1 of correspondence i, or NULL
+    const int64_t* idx1;
+    const int32_t* counts;
+    const double* K0;         // (P, 3, 3)
+    const double* K1;
+    const double* R;          // triangulate: (P, 3, 3), (P, 3)
+    const double* t;
+    const double* E;          // recover pose: (P, 3, 3)
+    const unsigned char* mask_in;   // (P, cap) or NULL
+    int n_const, P, cap, kcap;
+    double thr2, cos_min, max_depth;
+    float* X;                 // (P, cap, 3) (recover pose: or NULL)
+    float* Xref;              // (P, kcap, 3) or NULL, pre-filled with NaN
+    unsigned char* status;
+    float* err;
+    int32_t* info;
+    double* Rout;             // recover pose
+    double* tout;
+    int32_t* good;
+    unsigned char* mask_out;
+};
+
+// correspondence i of a pair through the index lists when given; false: an index outside [0, kcap).  r0 = its row of image 0
+struct TgView {
+    const float* p0;
+    const float* p1;
+    const int64_t* i0;
+    const int64_t* i1;
+    unsigned long long kcap;
+    __device__ TgView(const TgArgs& a, int pair)
+        : p0(a.p0 + (size_t)pair * a.kcap * 2), p1(a.p1 + (size_t)pair * a.kcap * 2), i0(a.idx0 ? a.idx0 + (size_t)pair * a.cap : nullptr),
+          i1(a.idx1 ? a.idx1 + (size_t)pair * a.cap : nullptr), kcap((unsigned long long)a.kcap) {}
+    __device__ inline bool get(int i, float4& q, unsigned long long& r0) const {
+        r0 = i0 ? (unsigned long long)i0[i] : (unsigned long long)i;
+        const unsigned long long r1 = i1 ? (unsigned long long)i1[i] : (unsigned long long)i;
+        const bool in = r0 < kcap && r1 < kcap;              // (a negative index is a huge unsigned one)
+        const float nanv = __builtin_nanf("");
+        q = make_float4(nanv, nanv, nanv, nanv);
+        if (in) {
+            const float2 a = *reinterpret_cast<const float2*>(p0 + 2 * r0);
+            const float2 b = *reinterpret_cast<const float2*>(p1 + 2 * r1);
+            q = make_float4(a.x, a.y, b.x, b.y);
+        }
+        return in;
+    }
+};
+
+// cal = fx0 fy0 cx0 cy0 fx1 fy1 cx1 cy1 of a pair: entry j of that list is entry tg_cal_src(j) of K0 (j < 4) or K1
+__device__ inline int tg_cal_src(int j) {
+    const int k = j & 3;
+    return k == 0 ? 0 : (k == 1 ? 4 : (k == 2 ? 2 : 5));
+}
+
+__global__ __launch_bounds__(256) void triangulate_kernel(TgArgs a) {
+    __shared__ double ps[20];                              // R (9), t (3), cal (8)
+    const int pair = blockIdx.y, tid = threadIdx.x;
+    const int n = rs::pair_count(a, pair);
+    const int i = blockIdx.x * 256 + tid;
+    if (tid < 9) ps[tid] = a.R[(size_t)pair * 9 + tid];
+    else if (tid < 12) ps[tid] = a.t[(size_t)pair * 3 + (tid - 9)];
+    else if (tid < 20) ps[tid] = (tid < 16 ? a.K0 : a.K1)[(size_t)pair * 9 + tg_cal_src(tid - 12)];
+    __syncthreads();
+    double R[9], t[3], cal[8], E[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = ps[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = ps[9 + k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cal[k] = ps[12 + k];
+    tg_pose_E(R, t, E);
+    const bool usable = tg_pose_ok(R, t);
+    const bool counted = i < n;                            // (n <= cap)
+    int st = tg::MASKED;
+    if (counted) {
+        const TgView pts(a, pair);
+        float4 q;
+        unsigned long long r0;
+        const bool in = pts.get(i, q, r0);
+        const bool masked = a.mask_in && a.mask_in[(size_t)pair * a.cap + i] == 0;
+        float X3[3], err;
+        double gate[4];
+        st = tg_point(R, t, E, usable, cal, (double)q.x, (double)q.y, (double)q.z, (double)q.w, masked, a.thr2, a.cos_min, a.max_depth, X3, err, gate);
+        const size_t o = (size_t)pair * a.cap + i;
+        a.X[3 * o] = X3[0]; a.X[3 * o + 1] = X3[1]; a.X[3 * o + 2] = X3[2];
+        a.status[o] = (unsigned char)st;
+        a.err[o] = err;
+        if (a.Xref && st == tg::VALID && in) {
+            float* ref = a.Xref + ((size_t)pair * a.kcap + (size_t)r0) * 3;
+            ref[0] = X3[0]; ref[1] = X3[1]; ref[2] = X3[2];
+        }
+    } else if (i < a.cap) {                                // beyond the pair's count: written, not counted
+        const size_t o = (size_t)pair * a.cap + i;
+        const float nanv = __builtin_nanf("");
+        a.X[3 * o] = nanv; a.X[3 * o + 1] = nanv; a.X[3 * o + 2] = nanv;
+        a.status[o] = (unsigned char)tg::MASKED;
+        a.err[o] = nanv;
+    }
+    // ---- status counts: one ballot per status, one atomic per wave and status
+    int32_t* info = a.info + (size_t)pair * 8;
+    const bool lead = (tid & 63) == 0;
+#pragma unroll
+    for (int s = 0; s < tg::NSTATUS; ++s) {
+        const unsigned long long m = __ballot(counted && st == s);
+        if (lead && m) atomicAdd(info + 1 + s, (int)__popcll(m));
+    }
+    if (blockIdx.x == 0 && tid == 0) info[0] = n;          // (the counts were zeroed before the launch; nobody adds to word 0)
+}
+
+__global__ __launch_bounds__(256) void recover_pose_kernel(TgArgs a) {
+    __shared__ double es[20];                              // E (9), 3 unused, cal (8)
+    __shared__ int cnt[4];
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const int n = rs::pair_count(a, pair);
+    if (tid < 9) es[tid] = a.E[(size_t)pair * 9 + tid];
+    else if (tid >= 12 && tid < 20) es[tid] = (tid < 16 ? a.K0 : a.K1)[(size_t)pair * 9 + tg_cal_src(tid - 12)];
+    if (tid < 4) cnt[tid] = 0;
+    __syncthreads();
+    double Ein[9], cal[8], Ra[9], Rb[9], t[3], En[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Ein[k] = es[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cal[k] = es[12 + k];
+    const bool usable = tg_decompose(Ein, Ra, Rb, t, En);
+    const TgView pts(a, pair);
+    const unsigned char* mask_in = a.mask_in ? a.mask_in + (size_t)pair * a.cap : nullptr;
+    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    for (int i = tid; i < n; i += 256) {
+        float4 q;
+        unsigned long long r0;
+        pts.get(i, q, r0);
+        if (mask_in && mask_in[i] == 0) continue;
+        const TgRays ry = tg_correct(En, cal, (double)q.x, (double)q.y, (double)q.z, (double)q.w);
+        double X[3];
+        c0 += tg_vote<0>(Ra, Rb, t, usable, ry, a.max_depth, X) == tg::VALID ? 1 : 0;
+        c1 += tg_vote<1>(Ra, Rb, t, usable, ry, a.max_depth, X) == tg::VALID ? 1 : 0;
+        c2 += tg_vote<2>(Ra, Rb, t, usable, ry, a.max_depth, X) == tg::VALID ? 1 : 0;
+        c3 += tg_vote<3>(Ra, Rb, t, usable, ry, a.max_depth, X) == tg::VALID ? 1 : 0;
+    }
+    if (c0) atomicAdd(&cnt[0], c0);
+    if (c1) atomicAdd(&cnt[1], c1);
+    if (c2) atomicAdd(&cnt[2], c2);
+    if (c3) atomicAdd(&cnt[3], c3);
+    __syncthreads();
+    const int g0 = cnt[0], g1 = cnt[1], g2 = cnt[2], g3 = cnt[3];
+    const int w = tg_winner(g0, g1, g2, g3);
+    const int best = w == 0 ? g0 : (w == 1 ? g1 : (w == 2 ? g2 : g3));
+    const bool found = usable && best > 0;
+    // ---- the winner's mask and points
+    double Rw[9], tw[3];
+    const double sg = (w & 1) ? -1.0 : 1.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rw[k] = w < 2 ? Ra[k] : Rb[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tw[k] = sg * t[k];
+    unsigned char* mask = a.mask_out + (size_t)pair * a.cap;
+    float* Xo = a.X ? a.X + (size_t)pair * a.cap * 3 : nullptr;
+    const float nanv = __builtin_nanf("");
+    for (int i = tid; i < a.cap; i += 256) {
+        bool pass = false;
+        double X[3] = {0.0, 0.0, 0.0};
+        if (found && i < n && !(mask_in && mask_in[i] == 0)) {
+            float4 q;
+            unsigned long long r0;
+            pts.get(i, q, r0);
+            const TgRays ry = tg_correct(En, cal, (double)q.x, (double)q.y, (double)q.z, (double)q.w);
+            double l0, l1, zz, r[3];
+            tg_depths(Rw, tw, ry, l0, l1, zz, r);
+            pass = tg_depth_status(usable, ry, l0, l1, zz, a.max_depth, X) == tg::VALID;
+        }
+        mask[i] = pass ? 1 : 0;
+        if (Xo) { Xo[3 * i] = pass ? (float)X[0] : nanv; Xo[3 * i + 1] = pass ? (float)X[1] : nanv; Xo[3 * i + 2] = pass ? (float)X[2] : nanv; }
+    }
+    if (tid == 0) {
+        double* Ro = a.Rout + (size_t)pair * 9;
+        double* to = a.tout + (size_t)pair * 3;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Ro[k] = found ? Rw[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) to[k] = found ? tw[k] : 0.0;
+        int32_t* good = a.good + (size_t)pair * 4;
+        good[0] = usable ? g0 : 0; good[1] = usable ? g1 : 0; good[2] = usable ? g2 : 0; good[3] = usable ? g3 : 0;
+        int32_t* info = a.info + (size_t)pair * 8;         // the family's words: found, winner (pose index), 0, votes of the winner, 0, n, 0, 0
+        info[0] = found ? 1 : 0; info[1] = found ? w : -1; info[2] = 0; info[3] = found ? best : 0; info[4] = 0; info[5] = n; info[6] = 0; info[7] = 0;
+    }
+}
+
+static TgArgs tg_args(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
+                      int cap, const double* K0, const double* K1, const unsigned char* mask_in) {
+    TgArgs a = {};
+    a.p0 = p0; a.p1 = p1; a.idx0 = idx0; a.idx1 = idx1; a.kcap = idx0 ? kcap : cap; a.counts = counts; a.n_const = n_const; a.P = P; a.cap = cap;
+    a.K0 = K0; a.K1 = K1; a.mask_in = mask_in;
+    return a;
+}
+
+int launch_triangulate(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
+                       int cap, const double* K0, const double* K1, const double* R, const double* t, const unsigned char* mask_in,
+                       double max_reproj_error, double cos_min, double max_depth, float* X, unsigned char* status, float* err, int32_t* info,
+                       float* Xref, hipStream_t st) {
+    if (P < 1 || P > 65535 || cap < 1) return -1;
+    TgArgs a = tg_args(p0, p1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, mask_in);
+    a.R = R; a.t = t; a.thr2 = max_reproj_error * max_reproj_error; a.cos_min = cos_min; a.max_depth = max_depth;
+    a.X = X; a.status = status; a.err = err; a.info = info; a.Xref = idx0 ? Xref : nullptr;
+    if (hipMemsetAsync(info, 0, (size_t)P * 8 * sizeof(int32_t), st) != hipSuccess) return -1;
+    if (a.Xref && hipMemsetAsync(a.Xref, 0xFF, (size_t)P * a.kcap * 3 * sizeof(float), st) != hipSuccess) return -1;     // all ones: a NaN
+    triangulate_kernel<<<dim3(ceil_div(cap, 256), P), 256, 0, st>>>(a);
+    return 0;
+}
+
+int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
+                        int cap, const double* K0, const double* K1, const double* E, const unsigned char* mask_in, double distance_thresh, double* R,
+                        double* t, int32_t* good, unsigned char* mask, float* X, int32_t* info, hipStream_t st) {
+    if (P < 1 || P > 65535 || cap < 1) return -1;
+    TgArgs a = tg_args(p0, p1, idx0, idx1, kcap, counts, n_const, P, cap, K0, K1, mask_in);
+    a.E = E; a.max_depth = distance_thresh; a.Rout = R; a.tout = t; a.good = good; a.mask_out = mask; a.X = X; a.info = info;
+    recover_pose_kernel<<<P, 256, 0, st>>>(a);
+    return 0;
+}
+
+}  // namespace xfh

@@ -117,6 +117,14 @@ size_t abspose_workspace_bytes(int P, int max_iters);
 int launch_estimate_abspose(const float* p2, const float* p3, const int64_t* idx2, const int64_t* idx3, int cap2, int cap3, const int32_t* counts,
                             int n_const, int P, int cap, const double* K, double max_err, int min_iters, int max_iters, double success_prob,
                             unsigned long long seed, double* R, double* t, unsigned char* mask, int32_t* info, void* ws, hipStream_t st);
+// ---- k_triangulate.hip (two-view structure: triangulation under a pose, the pose of an E by the points in front of both cameras; no workspace) ----
+int launch_triangulate(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
+                       int cap, const double* K0, const double* K1, const double* R, const double* t, const unsigned char* mask_in,
+                       double max_reproj_error, double cos_min, double max_depth, float* X, unsigned char* status, float* err, int32_t* info,
+                       float* Xref, hipStream_t st);
+int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
+                        int cap, const double* K0, const double* K1, const double* E, const unsigned char* mask_in, double distance_thresh, double* R,
+                        double* t, int32_t* good, unsigned char* mask, float* X, int32_t* info, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

@@ -422,6 +422,54 @@ int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* po
                                  void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Two-view structure: the 3D points of the correspondences under a relative pose, and the pose of an essential matrix
+ *     n, R, t, mask = cv2.recoverPose(E, points1, points2, cameraMatrix[, distanceThresh])    (modules/eval/scannet1500.py:84)
+ * for P pairs at once.  OpenCV is not available offline, so nothing is pinned to it: Lindstrom's optimal correction
+ * (niter2) and the closed-form depths of the corrected rays, as specified in DESIGN.md 3.14 / csrc/k_triangulate.hip.
+ * No workspace.  Every argument check returns before any launch.
+ *   pts0/pts1, counts/n_const, K0/K1 and the _matches forms (kpts + idx0/idx1 + n_matches; kpt_cap rows per key-point
+ *   list): as for xfh_estimate_relpose.  An index outside [0, kpt_cap) makes the correspondence "not finite".
+ *   xfh_triangulate: R (P,3,3), t (P,3) fp64 with X1 = R X0 + t (the outputs of xfh_estimate_relpose; zeros = no pose);
+ *     mask (P,cap) uint8 or NULL: a zero masks the correspondence out; max_reproj_error in pixels (positive, finite);
+ *     cos_min = cos(minimal parallax angle), in [-1, 1]; max_depth > 0 in the unit of t (+inf: no limit).
+ *     points3d (P,cap,3) fp32 in camera 0's frame, NaN unless status is 0; status (P,cap) uint8: XFH_TRI_*;
+ *     reproj_error (P,cap) fp32 pixels, NaN for XFH_TRI_MASKED / XFH_TRI_NOT_FINITE; rows at or beyond the pair's count are
+ *     written as masked.  info (P,8) int32: n, valid, masked, not finite, behind, far, reprojection, parallax (of the n rows).
+ *     points3d_ref (P,kpt_cap,3) fp32 or NULL (_matches only): the valid points at image 0's key-point rows idx0[i], NaN
+ *     elsewhere -- what xfh_estimate_abspose_matches takes as points3d.  One-to-one index lists are the contract; with
+ *     duplicate rows in idx0 a row holds one of its candidates.
+ *   xfh_recover_pose: E (P,3,3) fp64 at any scale or sign (x1' E x0 = 0 in calibrated coordinates; E = K1' F K0 for an F);
+ *     mask_in as above; distance_thresh > 0 (+inf: no limit).  R, t (unit) of the pose, of the four E decomposes into, under
+ *     which most correspondences have a depth in (0, distance_thresh) in both cameras (ties: the lower pose index, order
+ *     (Ra,t) (Ra,-t) (Rb,t) (Rb,-t)); good (P,4) int32 the four counts; mask (P,cap) uint8 = mask_in and passes under the
+ *     winner; points3d (P,cap,3) fp32 or NULL: the winner's points, NaN where the mask is 0; info (P,8) int32: found, pose
+ *     index (-1: none), 0, the winner's count, 0, n, 0, 0.  An unusable E or a best count of 0: found = 0 and zeros.
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_TRI_VALID 0
+#define XFH_TRI_MASKED 1
+#define XFH_TRI_NOT_FINITE 2
+#define XFH_TRI_BEHIND 3
+#define XFH_TRI_FAR 4
+#define XFH_TRI_REPROJ 5
+#define XFH_TRI_PARALLAX 6
+int xfh_triangulate(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap,
+                    const double* K0, const double* K1, const double* R, const double* t, const uint8_t* mask,
+                    double max_reproj_error, double cos_min, double max_depth, float* points3d, uint8_t* status,
+                    float* reproj_error, int32_t* info, xfh_stream stream);
+int xfh_triangulate_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                            const int32_t* n_matches, int P, int cap, const double* K0, const double* K1, const double* R,
+                            const double* t, const uint8_t* mask, double max_reproj_error, double cos_min, double max_depth,
+                            float* points3d, uint8_t* status, float* reproj_error, int32_t* info, float* points3d_ref,
+                            xfh_stream stream);
+int xfh_recover_pose(const float* pts0, const float* pts1, const int32_t* counts, int n_const, int P, int cap,
+                     const double* K0, const double* K1, const double* E, const uint8_t* mask_in, double distance_thresh,
+                     double* R, double* t, int32_t* good, uint8_t* mask, float* points3d, int32_t* info, xfh_stream stream);
+int xfh_recover_pose_matches(const float* kpts0, const float* kpts1, int kpt_cap, const int64_t* idx0, const int64_t* idx1,
+                             const int32_t* n_matches, int P, int cap, const double* K0, const double* K1, const double* E,
+                             const uint8_t* mask_in, double distance_thresh, double* R, double* t, int32_t* good, uint8_t* mask,
+                             float* points3d, int32_t* info, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
