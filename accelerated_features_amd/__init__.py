@@ -5,3 +5,5 @@
 from .xfeat import XFeat, XFeatModel  # noqa: F401
 from .structure import (essential_from_fundamental, recover_pose, recover_pose_batch, recover_pose_matches,  # noqa: F401
                         triangulate_batch, triangulate_matches)
+from .alignment import (apply_alignment, estimate_alignment_batch, estimate_alignment_matches,  # noqa: F401
+                        estimate_relative_pose_rgbd_matches)

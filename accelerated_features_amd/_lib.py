@@ -66,6 +66,10 @@ SIGNATURES = {
     "xfh_estimate_abspose": (_i, [_p, _p, _p, _i, _i, _i, _p, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_estimate_abspose_matches": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _p, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p,
                                           _sz, _p]),
+    "xfh_align_workspace_bytes": (_sz, [_i, _i]),
+    "xfh_estimate_alignment": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_estimate_alignment_matches": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, _i, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _p,
+                                            _p, _sz, _p]),
     "xfh_triangulate": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p]),
     "xfh_triangulate_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p,
                                      _p]),

@@ -106,3 +106,40 @@ def check_matches_2d3d(who, kpts2d, points3d, idx2d, idx3d, n_matches):
         if t.dtype != dt or not t.is_contiguous() or t.device != kpts2d.device:
             raise RuntimeError(f'{who}: contiguous float32 points, int64 indices, int32 counts on one device expected')
     return kpts2d.device, P, cap
+
+
+def check_points_3d3d(what, pts_a, pts_b, counts):
+    """Two (P, cap, 3) point lists (anything torch.as_tensor takes) and their counts or None -> float32 / int32 tensors on the device.
+    The shapes are checked before the device is asked for."""
+    pts_a, pts_b = torch.as_tensor(pts_a), torch.as_tensor(pts_b)
+    if pts_a.dim() != 3 or pts_a.shape[2] != 3 or pts_b.shape != pts_a.shape:
+        raise RuntimeError('expected two (P, cap, 3) point tensors of the same shape')
+    if counts is not None:
+        counts = torch.as_tensor(counts)
+        if counts.shape != (pts_a.shape[0],):
+            raise RuntimeError('counts must have one entry per pair')
+    dev = pts_a.device if pts_a.is_cuda else device(what)
+    pts_a, pts_b = pts_a.to(dev).float().contiguous(), pts_b.to(dev).float().contiguous()
+    if counts is not None:
+        counts = counts.to(dev).to(torch.int32).contiguous()
+    return pts_a, pts_b, counts, dev
+
+
+def check_matches_3d3d(who, points_a, points_b, idx_a, idx_b, n_matches):
+    """Two point tables (P,Ka,3), (P,Kb,3) float32 (Ka and Kb independent), idx (P,cap) int64, n_matches (P,) int32, all device-resident.
+    Returns (device, P, cap)."""
+    for t in (points_a, points_b, idx_a, idx_b, n_matches):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f'{who}: tensors expected')
+    if idx_a.dim() != 2:
+        raise RuntimeError('expected idx (P,cap)')
+    P, cap = idx_a.shape
+    if (points_a.dim() != 3 or points_b.dim() != 3 or points_a.shape[0] != P or points_b.shape[0] != P or points_a.shape[2] != 3
+            or points_b.shape[2] != 3 or idx_b.shape != idx_a.shape or n_matches.shape != (P,)):
+        raise RuntimeError('expected points_a (P,Ka,3), points_b (P,Kb,3), idx (P,cap), n_matches (P,)')
+    for t, dt in ((points_a, torch.float32), (points_b, torch.float32), (idx_a, torch.int64), (idx_b, torch.int64), (n_matches, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != points_a.device:
+            raise RuntimeError(f'{who}: contiguous float32 points, int64 indices, int32 counts on one device expected')
+    if not points_a.is_cuda:
+        raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
+    return points_a.device, P, cap

@@ -1040,6 +1040,46 @@ int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* po
                                  max_reproj_error, min_iters, max_iters, success_prob, seed, R, t, mask, info, workspace, workspace_bytes, stream);
 }
 
+// ---- 3D-3D alignment (k_align.hip)
+size_t xfh_align_workspace_bytes(int P, int max_iters) {
+    if (P <= 0 || max_iters <= 0) return 0;
+    return xfh::align_workspace_bytes(P, max_iters);
+}
+
+static int estimate_alignment_impl(const char* who, const float* pts_a, const float* pts_b, const int64_t* idx_a, const int64_t* idx_b, int cap_a, int cap_b,
+                                   const int32_t* counts, int n_const, int P, int cap, int with_scale, double max_error, int min_iters, int max_iters,
+                                   double success_prob, uint64_t seed, double* R, double* t, double* s, uint8_t* mask, int32_t* info, void* workspace,
+                                   size_t workspace_bytes, xfh_stream stream) {
+    if (!pts_a || !pts_b || !R || !t || !s || !mask || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (P <= 0 || P > 65535 || cap <= 0 || cap > (1 << 24) || cap_a <= 0 || cap_b <= 0 || (!counts && (n_const < 0 || n_const > cap)))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, n %d)", who, P, cap, n_const);
+    if (!(max_error > 0.0) || !(max_error <= 1.7976931348623157e308) || !(success_prob > 0.0 && success_prob < 1.0) || min_iters < 0)
+        return fail(XFH_ERR_ARG, "%s: max_error %g (positive, finite) / success_prob %g / min_iters %d", who, max_error, success_prob, min_iters);
+    if (max_iters < 1 || max_iters > 16384) return fail(XFH_ERR_UNSUPPORTED, "%s: max_iters %d outside [1, 16384]", who, max_iters);
+    int rc = check_ws(workspace, workspace_bytes, xfh::align_workspace_bytes(P, max_iters));
+    if (rc) return rc;
+    if (launch_estimate_alignment(pts_a, pts_b, idx_a, idx_b, cap_a, cap_b, counts, n_const, P, cap, with_scale, max_error, min_iters, max_iters,
+                                  success_prob, seed, R, t, s, mask, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: unsupported configuration", who);
+    return check_launch(who);
+}
+
+int xfh_estimate_alignment(const float* pts_a, const float* pts_b, const int32_t* counts, int n_const, int P, int cap, int with_scale, double max_error,
+                           int min_iters, int max_iters, double success_prob, uint64_t seed, double* R, double* t, double* s, uint8_t* mask,
+                           int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    return estimate_alignment_impl("xfh_estimate_alignment", pts_a, pts_b, nullptr, nullptr, cap, cap, counts, n_const, P, cap, with_scale, max_error,
+                                   min_iters, max_iters, success_prob, seed, R, t, s, mask, info, workspace, workspace_bytes, stream);
+}
+
+int xfh_estimate_alignment_matches(const float* points_a, int cap_a, const float* points_b, int cap_b, const int64_t* idx_a, const int64_t* idx_b,
+                                   const int32_t* n_matches, int P, int cap, int with_scale, double max_error, int min_iters, int max_iters,
+                                   double success_prob, uint64_t seed, double* R, double* t, double* s, uint8_t* mask, int32_t* info, void* workspace,
+                                   size_t workspace_bytes, xfh_stream stream) {
+    if (!idx_a || !idx_b || !n_matches) return fail(XFH_ERR_ARG, "xfh_estimate_alignment_matches: NULL argument");
+    return estimate_alignment_impl("xfh_estimate_alignment_matches", points_a, points_b, idx_a, idx_b, cap_a, cap_b, n_matches, 0, P, cap, with_scale,
+                                   max_error, min_iters, max_iters, success_prob, seed, R, t, s, mask, info, workspace, workspace_bytes, stream);
+}
+
 // ---- two-view structure (k_triangulate.hip): no workspace; every check returns before any launch
 static int structure_shape_check(const char* who, const float* pts0, const float* pts1, const double* K0, const double* K1, const int32_t* counts,
                                  int n_const, int P, int cap, int kcap) {

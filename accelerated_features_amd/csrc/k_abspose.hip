@@ -142,20 +142,7 @@ __device__ inline void ap_cosine_laws(double u, double v, double ra, double rc, 
 }
 // orthonormal frame (e1, e2, e3) of the triangle (A, B, C); false: degenerate (a zero first side, collinear)
 __device__ inline bool ap_frame(const double* A, const double* B, const double* Cc, double* e1, double* e2, double* e3) {
-    const double d1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-    const double d2[3] = {Cc[0] - A[0], Cc[1] - A[1], Cc[2] - A[2]};
-    const double n1 = tv::dot3(d1, d1);
-    const double r1 = sqrt(n1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) e1[k] = d1[k] / r1;
-    double c[3];
-    tv::cross3(e1, d2, c);
-    const double n3 = tv::dot3(c, c), n2 = tv::dot3(d2, d2);
-    const double r3 = sqrt(n3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) e3[k] = c[k] / r3;
-    tv::cross3(e3, e1, e2);
-    return n1 > 0.0 && n3 > ap::COLLINEAR_EPS2 * n2;
+    return tv::triangle_frame(A, B, Cc, ap::COLLINEAR_EPS2, e1, e2, e3);
 }
 // candidate poses of the sample: x[3], y[3] normalised image coordinates, X[9] the 3D points (point-major); out[12 c ..] = R (row-major),
 // t; returns their number (0: no model)

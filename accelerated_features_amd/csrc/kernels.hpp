@@ -117,6 +117,11 @@ size_t abspose_workspace_bytes(int P, int max_iters);
 int launch_estimate_abspose(const float* p2, const float* p3, const int64_t* idx2, const int64_t* idx3, int cap2, int cap3, const int32_t* counts,
                             int n_const, int P, int cap, const double* K, double max_err, int min_iters, int max_iters, double success_prob,
                             unsigned long long seed, double* R, double* t, unsigned char* mask, int32_t* info, void* ws, hipStream_t st);
+// ---- k_align.hip (3-point similarity / rigid RANSAC + closed-form refit: the transform between two sets of corresponding 3D points) ----
+size_t align_workspace_bytes(int P, int max_iters);
+int launch_estimate_alignment(const float* pa, const float* pb, const int64_t* idx_a, const int64_t* idx_b, int cap_a, int cap_b, const int32_t* counts,
+                              int n_const, int P, int cap, int with_scale, double max_err, int min_iters, int max_iters, double success_prob,
+                              unsigned long long seed, double* R, double* t, double* s, unsigned char* mask, int32_t* info, void* ws, hipStream_t st);
 // ---- k_triangulate.hip (two-view structure: triangulation under a pose, the pose of an E by the points in front of both cameras; no workspace) ----
 int launch_triangulate(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
                        int cap, const double* K0, const double* K1, const double* R, const double* t, const unsigned char* mask_in,

@@ -27,6 +27,25 @@ __device__ inline void cross3(const double* a, const double* b, double* c) {
 }
 __device__ inline double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
+// orthonormal frame (e1, e2, e3) of the triangle (A, B, C): e1 = (B - A) / |.|, e3 = (e1 x (C - A)) / |.|, e2 = e3 x e1; false: degenerate
+// (a zero first side, or sin^2 of the angle at A <= collinear_eps2).  Shared by k_abspose.hip (ap_frame) and k_align.hip (al_solve).
+__device__ inline bool triangle_frame(const double* A, const double* B, const double* Cc, double collinear_eps2, double* e1, double* e2, double* e3) {
+    const double d1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+    const double d2[3] = {Cc[0] - A[0], Cc[1] - A[1], Cc[2] - A[2]};
+    const double n1 = dot3(d1, d1);
+    const double r1 = sqrt(n1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e1[k] = d1[k] / r1;
+    double c[3];
+    cross3(e1, d2, c);
+    const double n3 = dot3(c, c), n2 = dot3(d2, d2);
+    const double r3 = sqrt(n3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e3[k] = c[k] / r3;
+    cross3(e3, e1, e2);
+    return n1 > 0.0 && n3 > collinear_eps2 * n2;
+}
+
 // Sampson error of x0 = (a, b, 1), x1 = (c, d, 1) under M = E or F (x1' M x0 = 0)
 __device__ inline double sampson(const double* M, double a, double b, double c, double d) {
     const double e0 = (M[0] * a + M[1] * b) + M[2], e1 = (M[3] * a + M[4] * b) + M[5], e2 = (M[6] * a + M[7] * b) + M[8];

@@ -422,6 +422,35 @@ int xfh_estimate_abspose_matches(const float* kpts2d, int cap2d, const float* po
                                  void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 3D-3D alignment: the similarity (with_scale != 0) or rigid (with_scale = 0, s = 1) transform B ~= s R A + t between two sets
+ * of corresponding 3D points, for P pairs at once -- the metric pose of an RGB-D pair, the scale between two
+ * reconstructions, the registration of a reconstruction to a metric frame.  RANSAC over a 3-point solver, MSAC on the point
+ * distance, a closed-form least-squares refit of the consensus set (Horn's quaternion method), as specified in DESIGN.md
+ * 3.15 / csrc/k_align.hip.
+ *   pts_a, pts_b (P,cap,3) fp32 (device), row i of one matches row i of the other; pair p uses its first counts[p] rows
+ *   (device int32; NULL: n_const for all).  A row with a coordinate that is not finite ("no point") is never sampled into a
+ *   model and never an inlier.  max_error is a distance in B's unit (positive, finite).  All max_iters (<= 16384; larger is
+ *   an error) hypotheses are scored on the device, the stopping rule (min_iters, success_prob) applied to the cost list
+ *   afterwards.
+ *   R (P,9) fp64 row-major (a proper rotation), t (P,3) fp64, s (P) fp64; mask (P,cap) uint8, 1 = |B - (s R A + t)| below
+ *   max_error; info (P,8) int32: found, winning hypothesis, hypotheses the loop would have run, inliers, accepted refits, n,
+ *   cost (lo, hi word).  Fewer than 3 correspondences / inliers: found = 0 and zeros in R, t, s and the mask.
+ *   xfh_estimate_alignment_matches: the same on two point tables (P,cap_a,3), (P,cap_b,3) -- the two capacities are
+ *   independent -- and index lists: correspondence i of pair p is (points_a[p][idx_a[p][i]], points_b[p][idx_b[p][i]]) for
+ *   i < n_matches[p]; idx (P,cap) int64.  An index outside its table makes the correspondence "no point".
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_align_workspace_bytes(int P, int max_iters);
+int xfh_estimate_alignment(const float* pts_a, const float* pts_b, const int32_t* counts, int n_const, int P, int cap,
+                           int with_scale, double max_error, int min_iters, int max_iters, double success_prob,
+                           uint64_t seed, double* R, double* t, double* s, uint8_t* mask, int32_t* info,
+                           void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_estimate_alignment_matches(const float* points_a, int cap_a, const float* points_b, int cap_b, const int64_t* idx_a,
+                                   const int64_t* idx_b, const int32_t* n_matches, int P, int cap, int with_scale,
+                                   double max_error, int min_iters, int max_iters, double success_prob, uint64_t seed,
+                                   double* R, double* t, double* s, uint8_t* mask, int32_t* info,
+                                   void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Two-view structure: the 3D points of the correspondences under a relative pose, and the pose of an essential matrix
  *     n, R, t, mask = cv2.recoverPose(E, points1, points2, cameraMatrix[, distanceThresh])    (modules/eval/scannet1500.py:84)
  * for P pairs at once.  OpenCV is not available offline, so nothing is pinned to it: Lindstrom's optimal correction
