@@ -443,4 +443,348 @@ int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, c
     return 0;
 }
 
+// ================================================================================================================================================
+// Multi-view triangulation of key-point tracks (tests/multiview_reference.py restates it operation for operation and
+// tests/test_multiview_emulated.py compiles the slice below, behind the slice above, on the host and holds it to that restatement bit for bit).
+// A call holds S scenes of up to V <= 32 views with PINHOLE intrinsics K_v and world -> camera poses x_v = R_v X + t_v; view 0 is the reference
+// view and a track is a row k of its key-point table: tracks[s, k, v] = the row of view v's table that track k sees, or -1.  Per track:
+//   * observed set O: views v < n_views[s] with a table entry in range, a finite pixel and a usable pose (entries finite, R not all zero;
+//     t = 0 is a pose here); 0 not in O or |O| < 2: status 1;
+//   * hypotheses, exhaustive: for v in O \ {0} ascending, Rrel = R_v R_0', trel = t_v - Rrel t_0 (zero: skipped), E = tg_pose_E, the point of
+//     the pair (0, v) by tg_correct / tg_depths / tg_depth_status with max_depth, moved to the world frame X = R_0' (X_c0 - t_0), scored by
+//     MSAC sum_{w in O} min(e_w^2, thr^2) (e_w^2 the squared pixel reprojection error of X in w; thr^2 where the depth in w is not > 0 or e_w^2
+//     is not finite); the lowest score wins, ties to the lowest v; no valid hypothesis: the failure code (2, 3, 4) of the lowest-v hypothesis
+//     tried (the error is then that pair's correction, as tg_point's), none tried: 2;
+//   * inliers I: w in O with depth > 0 and e_w^2 <= thr^2 under the winner, a 32-bit mask; 0 not in I or |I| < min_views: status 5;
+//   * refit: mv::GN_ITERS Gauss-Newton steps on sum_{w in I} e_w^2(X), I fixed, the 3x3 normal equations summed in ascending w and solved by
+//     cofactors; a step is kept only if it lowers the cost, otherwise the iteration stops;
+//   * final gates on the refined X over I, the first failing one wins: 2 not finite; 3 depth <= 0 in an inlier view; 4 depth > max_depth in one;
+//     5 max e_w^2 > thr^2; 6 min_{w in I \ {0}} cos(X - c_0, X - c_w) > cos_min (c_w = -R_w' t_w);
+//   * outputs: X as 3 fp32 (NaN unless the status is 0), the status, |I|, I, sqrt(max_{w in I} e_w^2) as fp32 (NaN for status 1 and 2).
+// Only + - * / sqrt, every product and sum rounded once, every sum over views in ascending view order.
+//
+// Launches (no workspace):
+//   track_scatter_kernel     : thread = match i of the pair (view 0, view v), grid = (chunks of 256 of max(cap, K), V - 1, S): an integer
+//                              atomicMax onto the table pre-filled with -1 (duplicate reference rows resolve to the largest candidate row:
+//                              reproducible); the threads of v = 1 also write column 0
+//   triangulate_views_kernel : thread = track, grid = (chunks of 256 of K, S); the first V threads of a workgroup put the per-view block
+//                              (mv::STRIDE doubles: R, t, calibration, centre, pose flag, Rrel, trel, E; 10.3 KB at V = 32) into LDS once;
+//                              every lane reads the same LDS address in the view loops (broadcasts); the observations are re-read from
+//                              global memory through the track table inside the loops; status counts as triangulate_kernel's
+
+// ---- views solver begin (host-compilable: tests/test_multiview_emulated.py slices it out behind the solver slice above) ----
+namespace mv {
+constexpr int MAX_VIEWS = 32;
+constexpr int GN_ITERS = 5;                 // the refit's steps (the cost stops moving after 3 at 0.5 - 2 px of noise)
+constexpr int UNOBSERVED = 1;               // the other status codes are tg::'s
+// the per-view block of doubles
+constexpr int ROT = 0, TRA = 9, CAL = 12, CEN = 16, OK = 19, RREL = 20, TREL = 29, ESS = 32, STRIDE = 41;
+}  // namespace mv
+
+// the per-view block of view v: Rv (9), tv (3) its pose, Kv (9, row-major) its intrinsics, R0, t0 the pose of view 0
+__device__ inline void mv_stage_view(const double* Rv, const double* tv, const double* Kv, const double* R0, const double* t0, double* o) {
+    bool fin = true, rnz = false;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[mv::TRA + k] = tv[k]; fin = fin && tv::is_finite(tv[k]); }
+    o[mv::CAL] = Kv[0]; o[mv::CAL + 1] = Kv[4]; o[mv::CAL + 2] = Kv[2]; o[mv::CAL + 3] = Kv[5];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[mv::CEN + i] = -((Rv[i] * tv[0] + Rv[3 + i] * tv[1]) + Rv[6 + i] * tv[2]);
+    o[mv::OK] = fin && rnz ? 1.0 : 0.0;
+    double Rrel[9], trel[3], E[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = (Rv[3 * i] * R0[3 * j] + Rv[3 * i + 1] * R0[3 * j + 1]) + Rv[3 * i + 2] * R0[3 * j + 2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) trel[i] = tv[i] - ((Rrel[3 * i] * t0[0] + Rrel[3 * i + 1] * t0[1]) + Rrel[3 * i + 2] * t0[2]);
+    tg_pose_E(Rrel, trel, E);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { o[mv::RREL + k] = Rrel[k]; o[mv::ESS + k] = E[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[mv::TREL + k] = trel[k];
+}
+// squared pixel reprojection error of the world point X in the view of block p against the pixel (u, v); z = its depth there
+__device__ inline double mv_reproj(const double* p, const double* X, double u, double v, double& z) {
+    const double x = ((p[0] * X[0] + p[1] * X[1]) + p[2] * X[2]) + p[mv::TRA];
+    const double y = ((p[3] * X[0] + p[4] * X[1]) + p[5] * X[2]) + p[mv::TRA + 1];
+    z = ((p[6] * X[0] + p[7] * X[1]) + p[8] * X[2]) + p[mv::TRA + 2];
+    const double du = (p[mv::CAL] * (x / z) + p[mv::CAL + 2]) - u, dv = (p[mv::CAL + 1] * (y / z) + p[mv::CAL + 3]) - v;
+    return du * du + dv * dv;
+}
+// the cost sum_{w in I} e_w^2 at X and its normal equations: A = J'J as (00 01 02 11 12 22), g = J'r.  obs(w, u, v) reads the pixel of view w.
+template <class Obs>
+__device__ inline double mv_normal(const double* vd, int nv, const Obs& obs, unsigned I, const double* X, double* A, double* g) {
+    double cost = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) A[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[k] = 0.0;
+    for (int w = 0; w < nv; ++w) {
+        if (!((I >> w) & 1u)) continue;
+        const double* p = vd + w * mv::STRIDE;
+        double u, v;
+        obs(w, u, v);
+        const double x = ((p[0] * X[0] + p[1] * X[1]) + p[2] * X[2]) + p[mv::TRA];
+        const double y = ((p[3] * X[0] + p[4] * X[1]) + p[5] * X[2]) + p[mv::TRA + 1];
+        const double z = ((p[6] * X[0] + p[7] * X[1]) + p[8] * X[2]) + p[mv::TRA + 2];
+        const double a = x / z, b = y / z;
+        const double du = (p[mv::CAL] * a + p[mv::CAL + 2]) - u, dv = (p[mv::CAL + 1] * b + p[mv::CAL + 3]) - v;
+        cost = cost + (du * du + dv * dv);
+        const double ju0 = p[mv::CAL] * ((p[0] - a * p[6]) / z), ju1 = p[mv::CAL] * ((p[1] - a * p[7]) / z), ju2 = p[mv::CAL] * ((p[2] - a * p[8]) / z);
+        const double jv0 = p[mv::CAL + 1] * ((p[3] - b * p[6]) / z), jv1 = p[mv::CAL + 1] * ((p[4] - b * p[7]) / z), jv2 = p[mv::CAL + 1] * ((p[5] - b * p[8]) / z);
+        A[0] = A[0] + (ju0 * ju0 + jv0 * jv0); A[1] = A[1] + (ju0 * ju1 + jv0 * jv1); A[2] = A[2] + (ju0 * ju2 + jv0 * jv2);
+        A[3] = A[3] + (ju1 * ju1 + jv1 * jv1); A[4] = A[4] + (ju1 * ju2 + jv1 * jv2); A[5] = A[5] + (ju2 * ju2 + jv2 * jv2);
+        g[0] = g[0] + (ju0 * du + jv0 * dv); g[1] = g[1] + (ju1 * du + jv1 * dv); g[2] = g[2] + (ju2 * du + jv2 * dv);
+    }
+    return cost;
+}
+// the Gauss-Newton step -A^-1 g of the symmetric A (00 01 02 11 12 22) by cofactors
+__device__ inline void mv_step(const double* A, const double* g, double* d) {
+    const double c00 = A[3] * A[5] - A[4] * A[4], c01 = A[2] * A[4] - A[1] * A[5], c02 = A[1] * A[4] - A[2] * A[3];
+    const double c11 = A[0] * A[5] - A[2] * A[2], c12 = A[1] * A[2] - A[0] * A[4], c22 = A[0] * A[3] - A[1] * A[1];
+    const double det = (A[0] * c00 + A[1] * c01) + A[2] * c02;
+    d[0] = -(((c00 * g[0] + c01 * g[1]) + c02 * g[2]) / det);
+    d[1] = -(((c01 * g[0] + c11 * g[1]) + c12 * g[2]) / det);
+    d[2] = -(((c02 * g[0] + c12 * g[1]) + c22 * g[2]) / det);
+}
+struct MvResult {
+    float X[3], err;           // NaN unless the status is 0; NaN for status 1 and 2
+    int status, n_inliers;
+    unsigned inliers;          // bit v = view v
+    int winner;                // the view of the winning hypothesis, -1: none
+    double score;              // its MSAC score (0 without a winner)
+    double cost0, cost1;       // the refit's cost before and after (0 without a refit)
+};
+// the per-track function: vd the per-view blocks, nv = n_views[s], obs(w, u, v) = the pixel of view w through the track table (false: no
+// entry in range; u, v then NaN)
+template <class Obs>
+__device__ inline MvResult mv_track(const double* vd, int nv, const Obs& obs, double thr2, double cos_min, double max_depth, int min_views) {
+    const float nanv = __builtin_nanf("");
+    MvResult o;
+    o.X[0] = nanv; o.X[1] = nanv; o.X[2] = nanv; o.err = nanv;
+    o.status = mv::UNOBSERVED; o.n_inliers = 0; o.inliers = 0u; o.winner = -1; o.score = 0.0; o.cost0 = 0.0; o.cost1 = 0.0;
+    // ---- the observed set
+    unsigned O = 0u;
+    int nobs = 0;
+    for (int w = 0; w < nv; ++w) {
+        double u, v;
+        const bool in = obs(w, u, v);
+        if (in && tv::is_finite(u) && tv::is_finite(v) && vd[w * mv::STRIDE + mv::OK] != 0.0) { O |= 1u << w; ++nobs; }
+    }
+    if (!(O & 1u) || nobs < 2) return o;
+    // ---- the hypotheses of the pairs (0, v)
+    double u0, v0;
+    obs(0, u0, v0);
+    double R0[9], t0[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R0[k] = vd[mv::ROT + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t0[k] = vd[mv::TRA + k];
+    int first = -1;
+    double first_e2 = 0.0, best = 0.0, X[3] = {0.0, 0.0, 0.0};
+    for (int v = 1; v < nv; ++v) {
+        if (!((O >> v) & 1u)) continue;
+        const double* p = vd + v * mv::STRIDE;
+        double Rrel[9], trel[3], E[9], cal[8];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) trel[k] = p[mv::TREL + k];
+        if (trel[0] == 0.0 && trel[1] == 0.0 && trel[2] == 0.0) continue;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { Rrel[k] = p[mv::RREL + k]; E[k] = p[mv::ESS + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { cal[k] = vd[mv::CAL + k]; cal[4 + k] = p[mv::CAL + k]; }
+        double uv, vv;
+        obs(v, uv, vv);
+        const TgRays q = tg_correct(E, cal, u0, v0, uv, vv);
+        double l0, l1, zz, r[3], Xc[3];
+        tg_depths(Rrel, trel, q, l0, l1, zz, r);
+        const int st = tg_depth_status(true, q, l0, l1, zz, max_depth, Xc);
+        if (first < 0) { first = st; first_e2 = q.e2; }
+        if (st != tg::VALID) continue;
+        const double d[3] = {Xc[0] - t0[0], Xc[1] - t0[1], Xc[2] - t0[2]};
+        double Xw[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Xw[i] = (R0[i] * d[0] + R0[3 + i] * d[1]) + R0[6 + i] * d[2];
+        double sc = 0.0;
+        for (int w = 0; w < nv; ++w) {
+            if (!((O >> w) & 1u)) continue;
+            double u, vpx, z;
+            obs(w, u, vpx);
+            const double e2 = mv_reproj(vd + w * mv::STRIDE, Xw, u, vpx, z);
+            sc = sc + (z > 0.0 && tv::is_finite(e2) && e2 < thr2 ? e2 : thr2);
+        }
+        if (o.winner < 0 || sc < best) { o.winner = v; best = sc; X[0] = Xw[0]; X[1] = Xw[1]; X[2] = Xw[2]; }
+    }
+    if (o.winner < 0) {
+        o.status = first < 0 ? tg::NOT_FINITE : first;
+        if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(first_e2);
+        return o;
+    }
+    o.score = best;
+    // ---- the inliers of the winner
+    unsigned I = 0u;
+    int ni = 0;
+    double emax = 0.0;
+    for (int w = 0; w < nv; ++w) {
+        if (!((O >> w) & 1u)) continue;
+        double u, vpx, z;
+        obs(w, u, vpx);
+        const double e2 = mv_reproj(vd + w * mv::STRIDE, X, u, vpx, z);
+        if (z > 0.0 && e2 <= thr2) { I |= 1u << w; ++ni; emax = e2 > emax ? e2 : emax; }
+    }
+    o.inliers = I; o.n_inliers = ni;
+    if (!(I & 1u) || ni < min_views) { o.status = tg::REPROJ; o.err = (float)sqrt(emax); return o; }
+    // ---- the refit on the fixed inlier set
+    double A[6], g[3];
+    double cost = mv_normal(vd, nv, obs, I, X, A, g);
+    o.cost0 = cost;
+    for (int it = 0; it < mv::GN_ITERS; ++it) {
+        double d[3], An[6], gn[3];
+        mv_step(A, g, d);
+        const double Xn[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
+        const double cn = mv_normal(vd, nv, obs, I, Xn, An, gn);
+        if (!(cn < cost)) break;
+        cost = cn; X[0] = Xn[0]; X[1] = Xn[1]; X[2] = Xn[2];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) A[k] = An[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k] = gn[k];
+    }
+    o.cost1 = cost;
+    // ---- the final gates
+    bool fin = tv::is_finite(X[0]) && tv::is_finite(X[1]) && tv::is_finite(X[2]), behind = false, far = false;
+    double cmin = 2.0;
+    emax = 0.0;
+    const double a[3] = {X[0] - vd[mv::CEN], X[1] - vd[mv::CEN + 1], X[2] - vd[mv::CEN + 2]};
+    const double aa = tv::dot3(a, a);
+    for (int w = 0; w < nv; ++w) {
+        if (!((I >> w) & 1u)) continue;
+        const double* p = vd + w * mv::STRIDE;
+        double u, vpx, z;
+        obs(w, u, vpx);
+        const double e2 = mv_reproj(p, X, u, vpx, z);
+        fin = fin && tv::is_finite(e2) && tv::is_finite(z);
+        behind = behind || !(z > 0.0);
+        far = far || z > max_depth;
+        emax = e2 > emax ? e2 : emax;
+        if (w > 0) {
+            const double b[3] = {X[0] - p[mv::CEN], X[1] - p[mv::CEN + 1], X[2] - p[mv::CEN + 2]};
+            const double c = tv::dot3(a, b) / sqrt(aa * tv::dot3(b, b));
+            cmin = c < cmin ? c : cmin;
+        }
+    }
+    o.status = !fin ? tg::NOT_FINITE : (behind ? tg::BEHIND : (far ? tg::FAR : (emax > thr2 ? tg::REPROJ : (cmin > cos_min ? tg::PARALLAX : tg::VALID))));
+    if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(emax);
+    if (o.status == tg::VALID) { o.X[0] = (float)X[0]; o.X[1] = (float)X[1]; o.X[2] = (float)X[2]; }
+    return o;
+}
+// ---- views solver end ----
+
+struct MvArgs {
+    const float* kpts;        // (S, V, kcap, 2)
+    const int32_t* tracks;    // (S, K, V)
+    const int32_t* n_views;   // (S,) or NULL: V
+    const double* Ks;         // (S, V, 3, 3)
+    const double* Rs;         // (S, V, 3, 3)
+    const double* ts;         // (S, V, 3)
+    int K, V, kcap, min_views;
+    double thr2, cos_min, max_depth;
+    float* X;                 // (S, K, 3)
+    unsigned char* status;    // (S, K)
+    unsigned char* n_inliers;
+    int32_t* inliers;
+    float* err;
+    int32_t* info;            // (S, 8)
+};
+
+// the pixel of view w of a track through its row of the table
+struct MvObs {
+    const int32_t* row;       // (V,)
+    const float* kp;          // (V, kcap, 2)
+    unsigned kcap;
+    __device__ inline bool operator()(int w, double& u, double& v) const {
+        const unsigned r = (unsigned)row[w];                 // (-1 is a huge unsigned one)
+        const bool in = r < kcap;
+        const float nanv = __builtin_nanf("");
+        float2 q = make_float2(nanv, nanv);
+        if (in) q = *reinterpret_cast<const float2*>(kp + ((size_t)w * kcap + r) * 2);
+        u = (double)q.x; v = (double)q.y;
+        return in;
+    }
+};
+
+__global__ __launch_bounds__(256) void triangulate_views_kernel(MvArgs a) {
+    __shared__ double vd[mv::MAX_VIEWS * mv::STRIDE];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const int k = blockIdx.x * 256 + tid;
+    int nv = a.n_views ? a.n_views[s] : a.V;
+    nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
+    if (tid < a.V) {
+        const size_t v = (size_t)s * a.V + tid, v0 = (size_t)s * a.V;
+        mv_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, a.Rs + v0 * 9, a.ts + v0 * 3, vd + tid * mv::STRIDE);
+    }
+    __syncthreads();
+    const bool counted = k < a.K;
+    int st = -1;
+    if (counted) {
+        const size_t o = (size_t)s * a.K + k;
+        MvObs obs;
+        obs.row = a.tracks + o * a.V; obs.kp = a.kpts + (size_t)s * a.V * a.kcap * 2; obs.kcap = (unsigned)a.kcap;
+        const MvResult r = mv_track(vd, nv, obs, a.thr2, a.cos_min, a.max_depth, a.min_views);
+        st = r.status;
+        a.X[3 * o] = r.X[0]; a.X[3 * o + 1] = r.X[1]; a.X[3 * o + 2] = r.X[2];
+        a.status[o] = (unsigned char)st;
+        a.n_inliers[o] = (unsigned char)r.n_inliers;
+        a.inliers[o] = (int32_t)r.inliers;
+        a.err[o] = r.err;
+    }
+    // ---- status counts: one ballot per status, one atomic per wave and status
+    int32_t* info = a.info + (size_t)s * 8;
+    const bool lead = (tid & 63) == 0;
+#pragma unroll
+    for (int c = 0; c < tg::NSTATUS; ++c) {
+        const unsigned long long m = __ballot(counted && st == c);
+        if (lead && m) atomicAdd(info + 1 + c, (int)__popcll(m));
+    }
+    if (blockIdx.x == 0 && tid == 0) info[0] = a.K;        // (the counts were zeroed before the launch; nobody adds to word 0)
+}
+
+// tracks (S, K, V) pre-filled with -1: column 0 = k, column v >= 1 = the largest row of view v that the list of the pair (0, v) gives row k
+__global__ __launch_bounds__(256) void track_scatter_kernel(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int V, int cap, int K,
+                                                            int kcap, int32_t* tracks) {
+    const int s = blockIdx.z, v = blockIdx.y + 1;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int32_t* tab = tracks + (size_t)s * K * V;
+    if (v == 1 && i < K) tab[(size_t)i * V] = i;
+    const size_t pair = (size_t)s * (V - 1) + (v - 1);
+    int n = cap > 0 ? n_matches[pair] : 0;
+    n = n > cap ? cap : n;
+    if (i >= n) return;
+    const unsigned long long r0 = (unsigned long long)idx_ref[pair * cap + i], r1 = (unsigned long long)idx_view[pair * cap + i];
+    if (r0 < (unsigned long long)K && r1 < (unsigned long long)kcap) atomicMax(tab + (size_t)r0 * V + v, (int)r1);
+}
+
+int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K, int kcap, int32_t* tracks,
+                        hipStream_t st) {
+    if (S < 1 || S > 65535 || V < 2 || V > mv::MAX_VIEWS || cap < 0 || K < 1 || kcap < 1) return -1;
+    if (hipMemsetAsync(tracks, 0xFF, (size_t)S * K * V * sizeof(int32_t), st) != hipSuccess) return -1;       // all ones: -1
+    track_scatter_kernel<<<dim3(ceil_div(cap > K ? cap : K, 256), V - 1, S), 256, 0, st>>>(idx_ref, idx_view, n_matches, V, cap, K, kcap, tracks);
+    return 0;
+}
+
+int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                             const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
+                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st) {
+    if (S < 1 || S > 65535 || K < 1 || V < 2 || V > mv::MAX_VIEWS || kcap < 1) return -1;
+    MvArgs a = {};
+    a.kpts = kpts; a.tracks = tracks; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts; a.K = K; a.V = V; a.kcap = kcap; a.min_views = min_views;
+    a.thr2 = max_reproj_error * max_reproj_error; a.cos_min = cos_min; a.max_depth = max_depth;
+    a.X = X; a.status = status; a.n_inliers = n_inliers; a.inliers = inliers; a.err = err; a.info = info;
+    if (hipMemsetAsync(info, 0, (size_t)S * 8 * sizeof(int32_t), st) != hipSuccess) return -1;
+    triangulate_views_kernel<<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
+    return 0;
+}
+
 }  // namespace xfh

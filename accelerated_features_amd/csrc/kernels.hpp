@@ -130,6 +130,12 @@ int launch_triangulate(const float* p0, const float* p1, const int64_t* idx0, co
 int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const, int P,
                         int cap, const double* K0, const double* K1, const double* E, const unsigned char* mask_in, double distance_thresh, double* R,
                         double* t, int32_t* good, unsigned char* mask, float* X, int32_t* info, hipStream_t st);
+// (multi-view triangulation of key-point tracks: the track table of a reference view, the point of each track from all the views that see it)
+int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K, int kcap, int32_t* tracks,
+                        hipStream_t st);
+int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                             const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
+                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

@@ -499,6 +499,34 @@ int xfh_recover_pose_matches(const float* kpts0, const float* kpts1, int kpt_cap
                              float* points3d, int32_t* info, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-view triangulation of key-point tracks: the point of every key-point of a reference view from all the views that see
+ * it, for S scenes at once (DESIGN.md 3.16 / csrc/k_triangulate.hip).  Scene s has n_views[s] <= V <= 32 views with PINHOLE
+ * intrinsics and world -> camera poses x_v = R_v X + t_v (the form xfh_estimate_abspose returns; (I, 0) and the R, t of
+ * xfh_estimate_relpose are the two-view case); view 0 is the reference view, a track is a row of its key-point table.
+ * No workspace.  Every argument check returns before any launch.
+ *   xfh_build_tracks: idx_ref, idx_view (S,V-1,cap) int64, n_matches (S,V-1) int32: the matcher's lists of the pairs
+ *     (view 0, view v), v = 1 .. V-1 (NULL allowed when cap is 0).  tracks (S,K,V) int32: [s,k,0] = k, [s,k,v] = the row of
+ *     view v (< kpt_cap) matched to row k of view 0, or -1; an index outside either table is ignored; of duplicate reference
+ *     rows the largest candidate row stays (reproducible).
+ *   xfh_triangulate_views: kpts (S,V,kpt_cap,2) fp32 pixels; tracks as above; n_views (S,) int32 or NULL (= V); Ks, Rs
+ *     (S,V,3,3), ts (S,V,3) fp64; max_reproj_error, cos_min, max_depth as for xfh_triangulate; min_views in [2, 32].
+ *     Per track: hypotheses of the pairs (0, v) scored by MSAC over the views that see it, the inlier views of the best one,
+ *     a Gauss-Newton refit on them, the gates.  points3d (S,K,3) fp32 in the world frame, NaN unless status is 0 (what
+ *     xfh_estimate_abspose_matches takes as points3d, indexed by the reference rows); status (S,K) uint8: XFH_TRI_* with
+ *     XFH_MV_UNOBSERVED for 1 (view 0 or every other view does not see the track); n_inliers (S,K) uint8; inlier_views (S,K)
+ *     int32, bit v = view v; reproj_error (S,K) fp32 = the largest inlier error in pixels, NaN for status 1 and 2; info (S,8)
+ *     int32: K, then the number of tracks per status 0 .. 6.
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_MV_UNOBSERVED 1
+#define XFH_MV_MAX_VIEWS 32
+int xfh_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K,
+                     int kpt_cap, int32_t* tracks, xfh_stream stream);
+int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V,
+                          const double* Ks, const double* Rs, const double* ts, double max_reproj_error, double cos_min,
+                          double max_depth, int min_views, float* points3d, uint8_t* status, uint8_t* n_inliers,
+                          int32_t* inlier_views, float* reproj_error, int32_t* info, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one

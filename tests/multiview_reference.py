@@ -1,0 +1,271 @@
+"""float64 numpy restatement of the multi-view triangulation of csrc/k_triangulate.hip: the per-view block (mv_stage_view),
+the per-track function (mv_track: observed set, the exhaustive hypotheses of the pairs (0, v) by structure_reference's tg_* restatements,
+MSAC scores, inlier views, the Gauss-Newton refit, the final gates) and the track table (a maximum-scatter).
+
+It performs the kernel's operations in the kernel's order, vectorised over the tracks of one scene (numpy never fuses a multiply and an add;
+a view that a track skips contributes an exact + 0.0 to its sums, which cannot change a sum that started at + 0.0), so its results are
+comparable bit for bit: the points and errors as float32, the status, the inlier mask, the winner, the score, the refit's costs.
+
+TEST INFRASTRUCTURE ONLY: nothing under ``accelerated_features_amd/`` imports it.
+"""
+import math
+
+import numpy as np
+
+import structure_reference as SR
+from oracle.twoview_reference import dot, finite
+
+VALID, UNOBSERVED, NOT_FINITE, BEHIND, FAR, REPROJ, PARALLAX = range(7)
+MAX_VIEWS = 32
+GN_ITERS = 5
+_ERR = dict(all="ignore")
+
+
+def build_tracks(idx_ref, idx_view, n_matches, K, kcap=None):
+    """One scene: idx_ref, idx_view (V-1, cap) integers, n_matches (V-1,).  tracks (K, V) int32: column 0 = k, column v the largest row of
+    view v among the matches of reference row k, -1 without one; an index outside [0, K) / [0, kcap) is ignored."""
+    idx_ref, idx_view = np.asarray(idx_ref, np.int64), np.asarray(idx_view, np.int64)
+    kcap = K if kcap is None else kcap
+    V = idx_ref.shape[0] + 1
+    cap = idx_ref.shape[1]
+    tracks = np.full((K, V), -1, np.int32)
+    tracks[:, 0] = np.arange(K)
+    for v in range(1, V):
+        n = min(max(int(n_matches[v - 1]), 0), cap)
+        a, b = idx_ref[v - 1, :n], idx_view[v - 1, :n]
+        ok = (a >= 0) & (a < K) & (b >= 0) & (b < kcap)
+        np.maximum.at(tracks[:, v], a[ok], b[ok].astype(np.int32))
+    return tracks
+
+
+def stage_view(Rv, tv, Kv, R0, t0):
+    """mv_stage_view: the per-view block as a dict of lists of float64 scalars."""
+    Rv, R0 = [np.float64(x) for x in np.asarray(Rv, np.float64).reshape(9)], [np.float64(x) for x in np.asarray(R0, np.float64).reshape(9)]
+    tv, t0 = [np.float64(x) for x in np.asarray(tv, np.float64).reshape(3)], [np.float64(x) for x in np.asarray(t0, np.float64).reshape(3)]
+    Kv = np.asarray(Kv, np.float64).reshape(9)
+    with np.errstate(**_ERR):
+        ok = all(bool(finite(x)) for x in Rv + tv) and any(bool(x != 0.0) for x in Rv)
+        cen = [-((Rv[i] * tv[0] + Rv[3 + i] * tv[1]) + Rv[6 + i] * tv[2]) for i in range(3)]
+        Rrel = [(Rv[3 * i] * R0[3 * j] + Rv[3 * i + 1] * R0[3 * j + 1]) + Rv[3 * i + 2] * R0[3 * j + 2] for i in range(3) for j in range(3)]
+        trel = [tv[i] - ((Rrel[3 * i] * t0[0] + Rrel[3 * i + 1] * t0[1]) + Rrel[3 * i + 2] * t0[2]) for i in range(3)]
+        E = SR.pose_E(Rrel, trel)
+    return dict(R=Rv, t=tv, cal=[Kv[0], Kv[4], Kv[2], Kv[5]], cen=cen, ok=ok, Rrel=Rrel, trel=trel, E=E)
+
+
+def reproj(p, X, u, v):
+    """mv_reproj: (e2, z) of the world points X (3 arrays) in the view of block p against the pixels (u, v)."""
+    R, t, cal = p["R"], p["t"], p["cal"]
+    with np.errstate(**_ERR):
+        x = ((R[0] * X[0] + R[1] * X[1]) + R[2] * X[2]) + t[0]
+        y = ((R[3] * X[0] + R[4] * X[1]) + R[5] * X[2]) + t[1]
+        z = ((R[6] * X[0] + R[7] * X[1]) + R[8] * X[2]) + t[2]
+        du, dv = (cal[0] * (x / z) + cal[2]) - u, (cal[1] * (y / z) + cal[3]) - v
+        return du * du + dv * dv, z
+
+
+def normal(views, nv, px, I, X):
+    """mv_normal: (cost, A (6 arrays: 00 01 02 11 12 22), g (3 arrays)) over the views of I (nv bool arrays)."""
+    n = X[0].shape[0]
+    cost, A, g = np.zeros(n), [np.zeros(n) for _ in range(6)], [np.zeros(n) for _ in range(3)]
+    with np.errstate(**_ERR):
+        for w in range(nv):
+            if not I[w].any():
+                continue
+            p = views[w]
+            R, t, cal = p["R"], p["t"], p["cal"]
+            u, v = px[w]
+            x = ((R[0] * X[0] + R[1] * X[1]) + R[2] * X[2]) + t[0]
+            y = ((R[3] * X[0] + R[4] * X[1]) + R[5] * X[2]) + t[1]
+            z = ((R[6] * X[0] + R[7] * X[1]) + R[8] * X[2]) + t[2]
+            a, b = x / z, y / z
+            du, dv = (cal[0] * a + cal[2]) - u, (cal[1] * b + cal[3]) - v
+            ju = [cal[0] * ((R[j] - a * R[6 + j]) / z) for j in range(3)]
+            jv = [cal[1] * ((R[3 + j] - b * R[6 + j]) / z) for j in range(3)]
+            add = lambda acc, term: acc + np.where(I[w], term, 0.0)      # noqa: E731
+            cost = add(cost, du * du + dv * dv)
+            for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+                A[k] = add(A[k], ju[i] * ju[j] + jv[i] * jv[j])
+            for i in range(3):
+                g[i] = add(g[i], ju[i] * du + jv[i] * dv)
+    return cost, A, g
+
+
+def step(A, g):
+    """mv_step: -A^-1 g by cofactors."""
+    with np.errstate(**_ERR):
+        c00, c01, c02 = A[3] * A[5] - A[4] * A[4], A[2] * A[4] - A[1] * A[5], A[1] * A[4] - A[2] * A[3]
+        c11, c12, c22 = A[0] * A[5] - A[2] * A[2], A[1] * A[2] - A[0] * A[4], A[0] * A[3] - A[1] * A[1]
+        det = (A[0] * c00 + A[1] * c01) + A[2] * c02
+        return [-(((c00 * g[0] + c01 * g[1]) + c02 * g[2]) / det), -(((c01 * g[0] + c11 * g[1]) + c12 * g[2]) / det),
+                -(((c02 * g[0] + c12 * g[1]) + c22 * g[2]) / det)]
+
+
+def _f32(v, keep):
+    with np.errstate(**_ERR):
+        return np.where(keep, v, np.nan).astype(np.float32)
+
+
+def triangulate_views(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=math.inf, min_views=2,
+                      pixels64=False, gn_iters=GN_ITERS):
+    """One scene: kpts (V, kcap, 2) float32 pixels (pixels64: taken as float64), tracks (K, V) integers, n_views an integer, Ks, Rs (V,3,3),
+    ts (V,3).  Returns a dict: points3d (K,3) float32, status (K,) uint8, n_inliers (K,) uint8, inlier_views (K,) int32, reproj_error (K,)
+    float32, info (8,), winner (K,) (-1: none), score, cost0, cost1 (K,) float64, X (K,3) float64 (the refined point wherever a refit ran) and
+    the gate quantities behind ``gate_margin``."""
+    kpts = np.asarray(kpts, np.float64 if pixels64 else np.float32).astype(np.float64)
+    tracks = np.asarray(tracks, np.int64)
+    V, kcap = kpts.shape[0], kpts.shape[1]
+    K = tracks.shape[0]
+    nv = min(max(int(n_views), 0), V)
+    thr2 = float(max_reproj_error) * float(max_reproj_error)
+    cos_min = math.cos(math.radians(float(min_parallax_deg)))
+    views = [stage_view(Rs[v], ts[v], Ks[v], Rs[0], ts[0]) for v in range(V)]
+    px, O = [], []
+    with np.errstate(**_ERR):
+        for w in range(nv):
+            r = tracks[:, w]
+            inr = (r >= 0) & (r < kcap)
+            q = kpts[w][np.where(inr, r, 0)] if kcap else np.zeros((K, 2))
+            u, v = np.where(inr, q[:, 0], np.nan), np.where(inr, q[:, 1], np.nan)
+            px.append((u, v))
+            O.append(inr & finite(u) & finite(v) & views[w]["ok"])
+        nobs = np.sum(O, axis=0) if nv else np.zeros(K, int)
+        started = (O[0] & (nobs >= 2)) if nv else np.zeros(K, bool)
+        # ---- hypotheses
+        first, first_e2 = np.full(K, -1), np.zeros(K)
+        winner, best, X = np.full(K, -1), np.zeros(K), [np.zeros(K) for _ in range(3)]
+        scores = np.full((max(nv, 1), K), np.inf)
+        hyp_l = []
+        R0, t0 = views[0]["R"], views[0]["t"]
+        for v in range(1, nv):
+            p = views[v]
+            if all(bool(x == 0.0) for x in p["trel"]):
+                continue
+            tried = started & O[v]
+            if not tried.any():
+                continue
+            cal = views[0]["cal"] + p["cal"]
+            q = SR.correct(p["E"], cal, px[0][0], px[0][1], px[v][0], px[v][1])
+            l0, l1, zz, _ = SR.depths(p["Rrel"], p["trel"], q)
+            st, Xc = SR.depth_status(True, q, l0, l1, zz, max_depth)
+            new = tried & (first < 0)
+            first, first_e2 = np.where(new, st, first), np.where(new, q["e2"], first_e2)
+            hyp_l.append((tried & (st != NOT_FINITE), l0, l1))
+            valid = tried & (st == SR.VALID)
+            d = [Xc[i] - t0[i] for i in range(3)]
+            Xw = [(R0[i] * d[0] + R0[3 + i] * d[1]) + R0[6 + i] * d[2] for i in range(3)]
+            sc = np.zeros(K)
+            for w in range(nv):
+                e2, z = reproj(views[w], Xw, *px[w])
+                sc = sc + np.where(O[w], np.where((z > 0.0) & finite(e2) & (e2 < thr2), e2, thr2), 0.0)
+            scores[v] = np.where(valid, sc, np.inf)
+            upd = valid & ((winner < 0) | (sc < best))
+            winner, best = np.where(upd, v, winner), np.where(upd, sc, best)
+            X = [np.where(upd, Xw[i], X[i]) for i in range(3)]
+        has = winner >= 0
+        # ---- inliers
+        I, win_e2, win_z = [], [], []
+        emax, ni = np.zeros(K), np.zeros(K, int)
+        for w in range(nv):
+            e2, z = reproj(views[w], X, *px[w])
+            inl = has & O[w] & (z > 0.0) & (e2 <= thr2)
+            I.append(inl); win_e2.append(np.where(has & O[w], e2, np.nan)); win_z.append(np.where(has & O[w], z, np.nan))
+            emax = np.where(inl & (e2 > emax), e2, emax)
+            ni = ni + inl
+        few = has & (~I[0] | (ni < min_views)) if nv else np.zeros(K, bool)
+        fit = has & ~few
+        Ifit = [i & fit for i in I]
+        # ---- refit
+        cost, A, g = normal(views, nv, px, Ifit, X)
+        cost0 = cost.copy()
+        act = fit.copy()
+        for _ in range(gn_iters):
+            d = step(A, g)
+            Xn = [X[i] + d[i] for i in range(3)]
+            cn, An, gn = normal(views, nv, px, Ifit, Xn)
+            act = act & (cn < cost)
+            if not act.any():
+                break
+            cost = np.where(act, cn, cost)
+            X = [np.where(act, Xn[i], X[i]) for i in range(3)]
+            A = [np.where(act, An[k], A[k]) for k in range(6)]
+            g = [np.where(act, gn[k], g[k]) for k in range(3)]
+        # ---- final gates
+        fin = finite(X[0]) & finite(X[1]) & finite(X[2])
+        behind, far = np.zeros(K, bool), np.zeros(K, bool)
+        cmin, emax2 = np.full(K, 2.0), np.zeros(K)
+        zmin, zmax = np.full(K, np.inf), np.full(K, -np.inf)
+        if nv:
+            a = [X[i] - views[0]["cen"][i] for i in range(3)]
+            aa = dot(a, a)
+        for w in range(nv):
+            p = views[w]
+            e2, z = reproj(p, X, *px[w])
+            m = Ifit[w]
+            fin = fin & (~m | (finite(e2) & finite(z)))
+            behind = behind | (m & ~(z > 0.0))
+            far = far | (m & (z > max_depth))
+            emax2 = np.where(m & (e2 > emax2), e2, emax2)
+            zmin, zmax = np.where(m & (z < zmin), z, zmin), np.where(m & (z > zmax), z, zmax)
+            if w > 0:
+                b = [X[i] - p["cen"][i] for i in range(3)]
+                c = dot(a, b) / np.sqrt(aa * dot(b, b))
+                cmin = np.where(m & (c < cmin), c, cmin)
+        st = np.full(K, VALID)
+        st = np.where(cmin > cos_min, PARALLAX, st)
+        st = np.where(emax2 > thr2, REPROJ, st)
+        st = np.where(far, FAR, st)
+        st = np.where(behind, BEHIND, st)
+        st = np.where(~fin, NOT_FINITE, st)
+        err2 = emax2
+        # the earlier exits, the earliest last
+        st, err2 = np.where(few, REPROJ, st), np.where(few, emax, err2)
+        nowin = started & ~has
+        st = np.where(nowin, np.where(first < 0, NOT_FINITE, first), st)
+        err2 = np.where(nowin, first_e2, err2)
+        st = np.where(~started, UNOBSERVED, st)
+        ok = st == VALID
+        pts = np.stack([_f32(X[i], ok) for i in range(3)], axis=1) if K else np.zeros((0, 3), np.float32)
+        err = _f32(np.sqrt(err2), (st != UNOBSERVED) & (st != NOT_FINITE))
+        mask = np.zeros(K, np.int64)
+        for w in range(nv):
+            mask |= I[w].astype(np.int64) << w
+    info = np.array([K] + [int((st == s).sum()) for s in range(7)], np.int32)
+    stack = lambda rows: np.stack(rows) if rows else np.zeros((0, K))      # noqa: E731
+    return dict(points3d=pts, status=st.astype(np.uint8), n_inliers=np.where(has, ni, 0).astype(np.uint8),
+                inlier_views=(mask & 0xFFFFFFFF).astype(np.uint32).view(np.int32), reproj_error=err, valid=ok, info=info, winner=winner,
+                score=np.where(has, best, 0.0), cost0=np.where(fit, cost0, 0.0), cost1=np.where(fit, cost, 0.0), X=np.stack(X, axis=1),
+                refit=fit, thr2=thr2, cos_min=cos_min, scores=scores, hyp_l=hyp_l, win_e2=stack(win_e2), win_z=stack(win_z), emax=emax2,
+                cmin=cmin, zmin=zmin, zmax=zmax, observed=stack(O).astype(bool), started=started)
+
+
+def gate_margin(r, max_depth=math.inf):
+    """The least relative distance of a track of a triangulate_views() result from a decision that a last-bit difference could flip: a
+    hypothesis' depth gates, a tie of the two best scores, the winner's inlier decisions (depth against 0, e^2 against thr^2) and the final
+    gates.  Above 1e-9 or so the discrete outputs of two bit-faithful implementations cannot differ."""
+    m = np.inf
+    thr2 = r["thr2"]
+    with np.errstate(**_ERR):
+        for live, l0, l1 in r["hyp_l"]:
+            for v in (l0[live], l1[live]):
+                m = min(m, np.min(np.abs(v) / np.maximum(1.0, np.abs(v)), initial=np.inf))
+                if math.isfinite(max_depth):
+                    m = min(m, np.min(np.abs(v - max_depth) / max_depth, initial=np.inf))
+        s = np.sort(r["scores"], axis=0)
+        if s.shape[0] >= 2:
+            two = np.isfinite(s[1])
+            m = min(m, np.min((s[1][two] - s[0][two]) / np.maximum(s[1][two], 1e-300), initial=np.inf))
+        e2, z = r["win_e2"], r["win_z"]
+        seen = ~np.isnan(z)
+        m = min(m, np.min(np.abs(z[seen]) / np.maximum(1.0, np.abs(z[seen])), initial=np.inf))
+        front = seen & (z > 0.0) & np.isfinite(e2)
+        m = min(m, np.min(np.abs(e2[front] - thr2) / thr2, initial=np.inf))
+        fit = r["refit"] & (r["status"] != NOT_FINITE)
+        for v in (r["zmin"][fit], r["zmax"][fit]):
+            m = min(m, np.min(np.abs(v) / np.maximum(1.0, np.abs(v)), initial=np.inf))
+            if math.isfinite(max_depth):
+                m = min(m, np.min(np.abs(v - max_depth) / max_depth, initial=np.inf))
+        past = fit & ((r["status"] == VALID) | (r["status"] >= REPROJ))
+        m = min(m, np.min(np.abs(r["emax"][past] - thr2) / thr2, initial=np.inf))
+        past = fit & ((r["status"] == VALID) | (r["status"] == PARALLAX))
+        m = min(m, np.min(np.abs(r["cmin"][past] - r["cos_min"]), initial=np.inf))
+    return float(m)
