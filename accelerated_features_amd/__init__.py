@@ -8,3 +8,4 @@ from .structure import (essential_from_fundamental, recover_pose, recover_pose_b
 from .alignment import (apply_alignment, estimate_alignment_batch, estimate_alignment_matches,  # noqa: F401
                         estimate_relative_pose_rgbd_matches)
 from .multiview import build_tracks, triangulate_views_batch, triangulate_views_matches  # noqa: F401
+from .multiview import bundle_adjust_batch, refine_views_batch  # noqa: F401

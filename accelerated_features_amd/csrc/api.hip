@@ -1187,6 +1187,33 @@ int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks,
     return check_launch(who);
 }
 
+// ---- bundle adjustment of poses and track points (k_triangulate.hip): every check returns before any launch
+size_t xfh_bundle_workspace_bytes(int S, int K, int V) {
+    if (S <= 0 || S > 65535 || K <= 0 || K > (1 << 24) || V < 2 || V > 32) return 0;
+    return xfh::bundle_workspace_bytes(S, K, V);
+}
+
+int xfh_bundle_adjust(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* inlier_views, const float* points3d,
+                      const int32_t* n_views, int S, int K, int V, const double* Ks, const double* Rs, const double* ts, uint32_t fixed_views,
+                      int max_iterations, double huber_px, double* Rs_out, double* ts_out, float* points3d_out, uint8_t* refined,
+                      int32_t* free_views, double* cost, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    const char* who = "xfh_bundle_adjust";
+    if (!kpts || !tracks || !inlier_views || !points3d || !Ks || !Rs || !ts || !Rs_out || !ts_out || !points3d_out || !refined || !free_views || !cost ||
+        !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (K < 1 || K > (1 << 24) || kpt_cap < 1) return fail(XFH_ERR_ARG, "%s: bad shape (K %d, key-point capacity %d)", who, K, kpt_cap);
+    if (max_iterations < 0 || max_iterations > 1000) return fail(XFH_ERR_ARG, "%s: max_iterations %d outside [0, 1000]", who, max_iterations);
+    if (!(huber_px > 0.0)) return fail(XFH_ERR_ARG, "%s: huber_px %g must be positive (+inf: plain squares)", who, huber_px);
+    int rc = check_ws(workspace, workspace_bytes, xfh::bundle_workspace_bytes(S, K, V));
+    if (rc) return rc;
+    if (launch_bundle_adjust(kpts, kpt_cap, tracks, inlier_views, points3d, n_views, S, K, V, Ks, Rs, ts, fixed_views, max_iterations, huber_px, Rs_out,
+                             ts_out, points3d_out, refined, free_views, cost, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

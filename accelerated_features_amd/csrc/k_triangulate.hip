@@ -787,4 +787,692 @@ int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks,
     return 0;
 }
 
+// ================================================================================================================================================
+// Bundle adjustment of the poses of the free views and the points of the valid tracks (tests/bundle_reference.py restates it
+// operation for operation and tests/test_bundle_emulated.py compiles the slice below, behind the two slices above, on the host and holds it
+// to that restatement bit for bit).  Levenberg-Marquardt with Marquardt scaling on sum rho(e_w), e_w^2 = mv_reproj's, rho = Huber's at c pixels:
+//   * observations, fixed at the input state: (k, w) with bit w of inlier_views[k], w < n_views, a table entry in range, a finite pixel, a
+//     usable pose, a finite input point, depth > 0 and a finite e_w^2; a track with fewer than 2 is not refined and its observations are
+//     dropped; a view is free when it is not in fixed_views and keeps at least ba::MIN_VIEW_OBS observations;
+//   * parameters: R <- R cay(w), t <- t + d (ba_pose_update: the update inside k_abspose.hip's ap_gn_update, restated) and X <- X + dX;
+//     dY/dw_j = R (e_j x X), dY/dd = I, dY/dX = R, the projection's derivative as mv_normal's;
+//   * one step at damping lambda, opl = 1 + lambda: per point V_k = sum_w wt Jp'Jp, g_k = -sum_w wt Jp'r in ascending w, the diagonal of V_k
+//     times opl, its inverse by cofactors (mv_step on the unit vectors); a determinant that is not finite or not > 0 holds the point for the
+//     step.  Reduced camera system, n = 6 V, lower triangle packed: block (w, v), v <= w, = [v == w] U_v* - sum_k Y_wk W_vk' with
+//     W_vk = wt Jc'Jp (6x3), Y_wk = W_wk V_k*^-1, the diagonal of U_v times opl term by term; rhs_v = sum_k (-wt Jc'r - Y_vk g_k); sums over
+//     tracks by rs::block_sums (thread i of 256 takes tracks i, i + 256, ...); rows of held views are identity and zero.  Cholesky with every
+//     element's subtractions in ascending column order, forward substitution ascending, back substitution descending; a pivot that is not
+//     > 0 or not finite fails the step.  Candidate points dX_k = V_k*^-1 (g_k - sum_w W_wk' d_w) over the free views in ascending w;
+//   * the candidate's cost is the robust sum (per track ascending w, per chunk of 256 tracks block_sums, chunks ascending); a depth <= 0 or a
+//     value that is not finite rejects; only a strictly lower finite cost is accepted: lambda <- max(lambda / 10, 1e-10), else
+//     lambda <- min(10 lambda, 1e10); a scene ends after max_iterations rounds, on a rejection with lambda at the ceiling, or when an
+//     accepted step lowers the cost by less than ba::FTOL relative.
+// Only + - * / sqrt, every product and sum rounded once, no floating-point atomics.
+//
+// Launches per call (workspace: bundle_workspace_bytes): ba_init_kernel (thread = track: masks, fp64 points, per-view counts by integer
+// atomics, cost partials), ba_setup_kernel (workgroup = scene: pose state, free views, status), then max_iterations rounds of ba_point_kernel
+// (thread = track: V_k*^-1, g_k: 72 B), ba_schur_kernel (workgroup = (view pair v <= w, scene): the Jacobians of the two views recomputed from
+// the poses in LDS, 36 or 42 block sums), ba_solve_kernel (workgroup = scene: the packed triangle in LDS, 148 KB at V = 32; candidate poses),
+// ba_update_kernel (thread = track: candidate point and cost partials), ba_decide_kernel (scene: accept or reject on the double-buffered
+// state), and ba_final_kernel (outputs).  The workgroups of a finished scene return at once; nothing synchronises with the host.
+
+// ---- bundle solver begin (host-compilable: tests/test_bundle_emulated.py slices it out behind the two slices above) ----
+namespace ba {
+constexpr int MIN_VIEW_OBS = 6;             // fewer observations than the 6 parameters of a pose: the view is held
+constexpr int STRIDE = 20;                  // the per-view block: mv::ROT, mv::TRA, mv::CAL, mv::OK of mv's block (what mv_reproj reads)
+constexpr double FTOL = 1e-8;               // noise-free scenes stop moving by more than 9.3e-9 relative once they are down to rounding
+constexpr double LAMBDA0 = 1e-3, LAMBDA_MIN = 1e-10, LAMBDA_MAX = 1e10;
+constexpr int ST_OK = 0, ST_NOTHING = 1, ST_NOT_FINITE = 2;
+}  // namespace ba
+
+__device__ inline void ba_stage_view(const double* Rv, const double* tv, const double* Kv, double* o) {
+    bool fin = true, rnz = false;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[mv::TRA + k] = tv[k]; fin = fin && tv::is_finite(tv[k]); o[mv::CEN + k] = 0.0; }
+    o[mv::CAL] = Kv[0]; o[mv::CAL + 1] = Kv[4]; o[mv::CAL + 2] = Kv[2]; o[mv::CAL + 3] = Kv[5];
+    o[mv::OK] = fin && rnz ? 1.0 : 0.0;
+}
+// Huber's rho of e^2 at c pixels (c = +inf: e^2) and the weight of the observation
+__device__ inline double ba_rho(double e2, double c, double& wt) {
+    const double e = sqrt(e2);
+    const bool far = e > c;
+    wt = far ? c / e : 1.0;
+    return far ? (2.0 * c) * e - c * c : e2;
+}
+// the observation set of a track at the input state (a mask of views; fewer than 2: none)
+template <class Obs>
+__device__ inline unsigned ba_mask(const double* vd, int nv, const Obs& obs, unsigned inl, const double* X) {
+    const bool xfin = tv::is_finite(X[0]) && tv::is_finite(X[1]) && tv::is_finite(X[2]);
+    unsigned M = 0u;
+    int n = 0;
+    for (int w = 0; w < nv; ++w) {
+        if (!((inl >> w) & 1u)) continue;
+        double u, v, z;
+        const bool in = obs(w, u, v);
+        const double* p = vd + w * ba::STRIDE;
+        if (!(in && tv::is_finite(u) && tv::is_finite(v) && p[mv::OK] != 0.0 && xfin)) continue;
+        const double e2 = mv_reproj(p, X, u, v, z);
+        if (z > 0.0 && tv::is_finite(e2)) { M |= 1u << w; ++n; }
+    }
+    return n >= 2 ? M : 0u;
+}
+// the robust cost of a track over its observations M; bad: an observation with depth <= 0 or a value that is not finite
+template <class Obs>
+__device__ inline double ba_cost(const double* vd, int nv, const Obs& obs, unsigned M, const double* X, double c, bool& bad) {
+    double cost = 0.0;
+    bad = false;
+    for (int w = 0; w < nv; ++w) {
+        if (!((M >> w) & 1u)) continue;
+        double u, v, z, wt;
+        obs(w, u, v);
+        const double e2 = mv_reproj(vd + w * ba::STRIDE, X, u, v, z);
+        bad = bad || !(z > 0.0) || !tv::is_finite(e2);
+        cost = cost + ba_rho(e2, c, wt);
+    }
+    return cost;
+}
+// one observation: residual (du, dv), weight, Jp = d(du, dv)/dX (u row, v row), Jc = d(du, dv)/d(w, d) (u row, v row)
+struct BaTerm {
+    double du, dv, wt;
+    double jp[6], jc[12];
+};
+__device__ inline void ba_term(const double* p, const double* X, double u, double v, double c, BaTerm& o) {
+    double z;
+    const double e2 = mv_reproj(p, X, u, v, z);
+    ba_rho(e2, c, o.wt);
+    const double x = ((p[0] * X[0] + p[1] * X[1]) + p[2] * X[2]) + p[mv::TRA];
+    const double y = ((p[3] * X[0] + p[4] * X[1]) + p[5] * X[2]) + p[mv::TRA + 1];
+    const double a = x / z, b = y / z;
+    o.du = (p[mv::CAL] * a + p[mv::CAL + 2]) - u; o.dv = (p[mv::CAL + 1] * b + p[mv::CAL + 3]) - v;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        o.jp[j] = p[mv::CAL] * ((p[j] - a * p[6 + j]) / z);
+        o.jp[3 + j] = p[mv::CAL + 1] * ((p[3 + j] - b * p[6 + j]) / z);
+    }
+    const double gu0 = p[mv::CAL] / z, gu2 = -((p[mv::CAL] * a) / z), gv1 = p[mv::CAL + 1] / z, gv2 = -((p[mv::CAL + 1] * b) / z);
+    // dY/dw_j = R (e_j x X): component i
+    const double d20 = p[8] * X[1] - p[7] * X[2], d21 = p[6] * X[2] - p[8] * X[0], d22 = p[7] * X[0] - p[6] * X[1];
+    const double d00 = p[2] * X[1] - p[1] * X[2], d01 = p[0] * X[2] - p[2] * X[0], d02 = p[1] * X[0] - p[0] * X[1];
+    const double d10 = p[5] * X[1] - p[4] * X[2], d11 = p[3] * X[2] - p[5] * X[0], d12 = p[4] * X[0] - p[3] * X[1];
+    o.jc[0] = gu0 * d00 + gu2 * d20; o.jc[1] = gu0 * d01 + gu2 * d21; o.jc[2] = gu0 * d02 + gu2 * d22;
+    o.jc[3] = gu0; o.jc[4] = 0.0; o.jc[5] = gu2;
+    o.jc[6] = gv1 * d10 + gv2 * d20; o.jc[7] = gv1 * d11 + gv2 * d21; o.jc[8] = gv1 * d12 + gv2 * d22;
+    o.jc[9] = 0.0; o.jc[10] = gv1; o.jc[11] = gv2;
+}
+// V_k*^-1 (00 01 02 11 12 22) and g_k of a track at opl = 1 + lambda; false: the point is held for this step
+template <class Obs>
+__device__ inline bool ba_point(const double* vd, int nv, const Obs& obs, unsigned M, const double* X, double c, double opl, double* Vi, double* g) {
+    double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, s[3] = {0.0, 0.0, 0.0};
+    for (int w = 0; w < nv; ++w) {
+        if (!((M >> w) & 1u)) continue;
+        double u, v;
+        obs(w, u, v);
+        BaTerm t;
+        ba_term(vd + w * ba::STRIDE, X, u, v, c, t);
+        A[0] = A[0] + t.wt * (t.jp[0] * t.jp[0] + t.jp[3] * t.jp[3]); A[1] = A[1] + t.wt * (t.jp[0] * t.jp[1] + t.jp[3] * t.jp[4]);
+        A[2] = A[2] + t.wt * (t.jp[0] * t.jp[2] + t.jp[3] * t.jp[5]); A[3] = A[3] + t.wt * (t.jp[1] * t.jp[1] + t.jp[4] * t.jp[4]);
+        A[4] = A[4] + t.wt * (t.jp[1] * t.jp[2] + t.jp[4] * t.jp[5]); A[5] = A[5] + t.wt * (t.jp[2] * t.jp[2] + t.jp[5] * t.jp[5]);
+        s[0] = s[0] + t.wt * (t.jp[0] * t.du + t.jp[3] * t.dv); s[1] = s[1] + t.wt * (t.jp[1] * t.du + t.jp[4] * t.dv);
+        s[2] = s[2] + t.wt * (t.jp[2] * t.du + t.jp[5] * t.dv);
+    }
+    g[0] = -s[0]; g[1] = -s[1]; g[2] = -s[2];
+    A[0] = A[0] * opl; A[3] = A[3] * opl; A[5] = A[5] * opl;
+    const double c00 = A[3] * A[5] - A[4] * A[4], c01 = A[2] * A[4] - A[1] * A[5], c02 = A[1] * A[4] - A[2] * A[3];
+    const double det = (A[0] * c00 + A[1] * c01) + A[2] * c02;
+    const double e0[3] = {-1.0, 0.0, 0.0}, e1[3] = {0.0, -1.0, 0.0}, e2[3] = {0.0, 0.0, -1.0};
+    double q0[3], q1[3], q2[3];
+    mv_step(A, e0, q0); mv_step(A, e1, q1); mv_step(A, e2, q2);
+    Vi[0] = q0[0]; Vi[1] = q0[1]; Vi[2] = q0[2]; Vi[3] = q1[1]; Vi[4] = q1[2]; Vi[5] = q2[2];
+    return tv::is_finite(det) && det > 0.0;
+}
+// W = wt Jc'Jp (6 rows of 3) of an observation, Y = W V^-1
+__device__ inline void ba_W(const BaTerm& t, double* W) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W[3 * a + c] = t.wt * (t.jc[a] * t.jp[c] + t.jc[6 + a] * t.jp[3 + c]);
+}
+__device__ inline void ba_Y(const double* W, const double* Vi, double* Y) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        Y[3 * a] = (W[3 * a] * Vi[0] + W[3 * a + 1] * Vi[1]) + W[3 * a + 2] * Vi[2];
+        Y[3 * a + 1] = (W[3 * a] * Vi[1] + W[3 * a + 1] * Vi[3]) + W[3 * a + 2] * Vi[4];
+        Y[3 * a + 2] = (W[3 * a] * Vi[2] + W[3 * a + 1] * Vi[4]) + W[3 * a + 2] * Vi[5];
+    }
+}
+// one track's term of block (row view, column view) of the reduced system: acc[6 a + b] (row 6 w + a, column 6 v + b); DIAG (row == column
+// view): also acc[36 + a], the right-hand side.  A held point takes no part in the products with V^-1.
+template <bool DIAG>
+__device__ inline void ba_pair_add(const BaTerm& tr, const BaTerm& tc, const double* Vi, const double* g, bool held, double opl, double* acc) {
+    double Wr[18], Wc[18], Y[18];
+    ba_W(tr, Wr);
+    ba_W(tc, Wc);
+    ba_Y(Wr, Vi, Y);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            const double s = held ? 0.0 : (Y[3 * a] * Wc[3 * b] + Y[3 * a + 1] * Wc[3 * b + 1]) + Y[3 * a + 2] * Wc[3 * b + 2];
+            if (DIAG) {
+                const double u = tr.wt * (tr.jc[a] * tr.jc[b] + tr.jc[6 + a] * tr.jc[6 + b]);
+                acc[6 * a + b] = acc[6 * a + b] + ((a == b ? u * opl : u) - s);
+            } else {
+                acc[6 * a + b] = acc[6 * a + b] - s;
+            }
+        }
+        if (DIAG) {
+            const double r = -(tr.wt * (tr.jc[a] * tr.du + tr.jc[6 + a] * tr.dv));
+            const double yg = held ? 0.0 : (Y[3 * a] * g[0] + Y[3 * a + 1] * g[1]) + Y[3 * a + 2] * g[2];
+            acc[36 + a] = acc[36 + a] + (r - yg);
+        }
+    }
+}
+// Cholesky of the packed lower triangle L (entry (i, j), j <= i, at i (i + 1) / 2 + j) in place (the diagonal keeps the pivots' squares, piv
+// their roots), then r <- the solution of L L' d = r.  Thread tid of nt; sync() is the workgroup's barrier (the host: one thread, nothing).
+// false: a pivot that is not > 0 or not finite (the same on every thread).
+template <class Sync>
+__device__ inline bool ba_cholesky_solve(double* L, double* r, double* piv, int n, int tid, int nt, const Sync& sync) {
+    sync();
+    for (int j = 0; j < n; ++j) {
+        const double* rj = L + (size_t)j * (j + 1) / 2;
+        for (int i = j + tid; i < n; i += nt) {
+            double* ri = L + (size_t)i * (i + 1) / 2;
+            double v = ri[j];
+            for (int q = 0; q < j; ++q) v = v - ri[q] * rj[q];
+            ri[j] = v;
+        }
+        sync();
+        const double d = rj[j];
+        if (!(d > 0.0) || !tv::is_finite(d)) return false;
+        const double pj = sqrt(d);
+        if (tid == 0) piv[j] = pj;
+        for (int i = j + 1 + tid; i < n; i += nt) {
+            double* ri = L + (size_t)i * (i + 1) / 2;
+            ri[j] = ri[j] / pj;
+        }
+        sync();
+    }
+    for (int q = 0; q < n; ++q) {                           // forward: every row's subtractions in ascending q
+        if (tid == 0) r[q] = r[q] / piv[q];
+        sync();
+        const double yq = r[q];
+        for (int i = q + 1 + tid; i < n; i += nt) r[i] = r[i] - L[(size_t)i * (i + 1) / 2 + q] * yq;
+        sync();
+    }
+    for (int q = n - 1; q >= 0; --q) {                      // back: every row's subtractions in descending q
+        if (tid == 0) r[q] = r[q] / piv[q];
+        sync();
+        const double dq = r[q];
+        const double* rq = L + (size_t)q * (q + 1) / 2;
+        for (int i = tid; i < q; i += nt) r[i] = r[i] - rq[i] * dq;
+        sync();
+    }
+    return true;
+}
+// R cay(w), t + d of d6 = (w, d) (the update inside k_abspose.hip's ap_gn_update, restated)
+__device__ inline void ba_pose_update(const double* R, const double* t, const double* d6, double* Rn, double* tn) {
+    const double w0 = d6[0], w1 = d6[1], w2 = d6[2];
+    const double n2 = (w0 * w0 + w1 * w1) + w2 * w2;
+    const double f = 1.0 / (1.0 + 0.25 * n2);
+    const double w[3] = {w0, w1, w2};
+    const double W[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+    double Cm[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double ww = w[i] * w[j] - (i == j ? n2 : 0.0);
+            Cm[3 * i + j] = (i == j ? 1.0 : 0.0) + f * (W[3 * i + j] + 0.5 * ww);
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (R[3 * i] * Cm[j] + R[3 * i + 1] * Cm[3 + j]) + R[3 * i + 2] * Cm[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tn[i] = t[i] + d6[3 + i];
+}
+// the candidate point of a track: X + V^-1 (g - sum_w W_wk' d_w) over its observations in the free views, ascending w; held: X
+template <class Obs>
+__device__ inline void ba_point_step(const double* vd, int nv, const Obs& obs, unsigned M, unsigned free_views, const double* X, double c,
+                                     const double* Vi, const double* g, bool held, const double* dcam, double* Xn) {
+    double q0 = g[0], q1 = g[1], q2 = g[2];
+    for (int w = 0; w < nv; ++w) {
+        if (!(((M & free_views) >> w) & 1u)) continue;
+        double u, v, W[18];
+        obs(w, u, v);
+        BaTerm t;
+        ba_term(vd + w * ba::STRIDE, X, u, v, c, t);
+        ba_W(t, W);
+        const double* d = dcam + 6 * w;
+        q0 = q0 - (((((W[0] * d[0] + W[3] * d[1]) + W[6] * d[2]) + W[9] * d[3]) + W[12] * d[4]) + W[15] * d[5]);
+        q1 = q1 - (((((W[1] * d[0] + W[4] * d[1]) + W[7] * d[2]) + W[10] * d[3]) + W[13] * d[4]) + W[16] * d[5]);
+        q2 = q2 - (((((W[2] * d[0] + W[5] * d[1]) + W[8] * d[2]) + W[11] * d[3]) + W[14] * d[4]) + W[17] * d[5]);
+    }
+    const double dx = (Vi[0] * q0 + Vi[1] * q1) + Vi[2] * q2, dy = (Vi[1] * q0 + Vi[3] * q1) + Vi[4] * q2, dz = (Vi[2] * q0 + Vi[4] * q1) + Vi[5] * q2;
+    Xn[0] = held ? X[0] : X[0] + dx; Xn[1] = held ? X[1] : X[1] + dy; Xn[2] = held ? X[2] : X[2] + dz;
+}
+// the decision of a round: the state words lambda, cost; returns accepted; done: the scene has ended
+__device__ inline bool ba_decide(bool failed, double cand, double& lambda, double& cost, bool& done) {
+    const bool accept = !failed && tv::is_finite(cand) && cand < cost;
+    if (accept) {
+        done = cost - cand < ba::FTOL * cost;
+        cost = cand;
+        const double l = lambda / 10.0;
+        lambda = l > ba::LAMBDA_MIN ? l : ba::LAMBDA_MIN;
+    } else {
+        done = lambda >= ba::LAMBDA_MAX;
+        const double l = 10.0 * lambda;
+        lambda = l < ba::LAMBDA_MAX ? l : ba::LAMBDA_MAX;
+    }
+    return accept;
+}
+// ---- bundle solver end ----
+
+struct BaCtrl {               // per scene
+    double lambda, cost, cost0;
+    int32_t cur, done, iters, accepted, status, free_views, failed, bad, n_refined, n_obs;
+};
+struct BaArgs {
+    const float* kpts;        // (S, V, kcap, 2)
+    const int32_t* tracks;    // (S, K, V)
+    const int32_t* inliers;   // (S, K)
+    const float* X0;          // (S, K, 3)
+    const int32_t* n_views;   // (S,) or NULL
+    const double* Ks;         // (S, V, 3, 3)
+    const double* Rs;
+    const double* ts;
+    int S, K, V, kcap, nch;
+    unsigned fixed;
+    double huber;
+    // workspace
+    BaCtrl* ctrl;             // (S,)
+    int32_t* counts;          // (S, 32) observations per view
+    double* pose;             // (S, 2, V, 12)
+    double* X;                // (S, 2, K, 3)
+    uint32_t* mask;           // (S, K)
+    unsigned char* held;      // (S, K)
+    double* pv;               // (S, K, 9): V*^-1 (6), g (3)
+    double* sys;              // (S, n (n + 1) / 2 + n), n = 6 V: the packed triangle, then the right-hand side
+    double* dcam;             // (S, n)
+    double* partial;          // (S, nch)
+    // outputs
+    double* Rout;
+    double* tout;
+    float* Xout;
+    unsigned char* refined;
+    int32_t* free_out;
+    double* cost_out;         // (S, 2)
+    int32_t* info;            // (S, 8)
+};
+
+__device__ inline int ba_nv(const BaArgs& a, int s) {
+    int nv = a.n_views ? a.n_views[s] : a.V;
+    return nv < 0 ? 0 : (nv > a.V ? a.V : nv);
+}
+__device__ inline MvObs ba_obs(const BaArgs& a, size_t o, int s) {
+    MvObs obs;
+    obs.row = a.tracks + o * a.V; obs.kp = a.kpts + (size_t)s * a.V * a.kcap * 2; obs.kcap = (unsigned)a.kcap;
+    return obs;
+}
+// the view blocks of scene s from buffer `which` of the pose state into LDS
+__device__ inline void ba_stage_state(const BaArgs& a, int s, int which, double* vd) {
+    const int tid = threadIdx.x;
+    if (tid < a.V) {
+        const double* p = a.pose + (((size_t)s * 2 + which) * a.V + tid) * 12;
+        ba_stage_view(p, p + 9, a.Ks + ((size_t)s * a.V + tid) * 9, vd + tid * ba::STRIDE);
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_init_kernel(BaArgs a) {
+    __shared__ double vd[mv::MAX_VIEWS * ba::STRIDE];
+    __shared__ double red[rs::block_sums_bytes(1) / sizeof(double)];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const int k = blockIdx.x * 256 + tid;
+    const int nv = ba_nv(a, s);
+    if (tid < a.V) {
+        const size_t v = (size_t)s * a.V + tid;
+        ba_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * ba::STRIDE);
+    }
+    __syncthreads();
+    unsigned M = 0u;
+    double cost[1] = {0.0};
+    if (k < a.K) {
+        const size_t o = (size_t)s * a.K + k;
+        const double X[3] = {(double)a.X0[3 * o], (double)a.X0[3 * o + 1], (double)a.X0[3 * o + 2]};
+        const MvObs obs = ba_obs(a, o, s);
+        M = ba_mask(vd, nv, obs, (unsigned)a.inliers[o], X);
+        bool bad;
+        if (M) cost[0] = ba_cost(vd, nv, obs, M, X, a.huber, bad);
+        double* Xs = a.X + ((size_t)s * 2 * a.K + k) * 3;
+        Xs[0] = X[0]; Xs[1] = X[1]; Xs[2] = X[2];
+        a.mask[o] = M;
+    }
+    const bool lead = (tid & 63) == 0;
+    int nobs = 0;
+    for (int w = 0; w < a.V; ++w) {
+        const unsigned long long m = __ballot((M >> w) & 1u);
+        if (lead && m) { atomicAdd(a.counts + (size_t)s * 32 + w, (int)__popcll(m)); nobs += (int)__popcll(m); }
+    }
+    const unsigned long long m = __ballot(M != 0u);
+    if (lead && m) atomicAdd(&a.ctrl[s].n_refined, (int)__popcll(m));
+    if (lead && nobs) atomicAdd(&a.ctrl[s].n_obs, nobs);
+    rs::block_sums(cost, red);
+    if (tid == 0) a.partial[(size_t)s * a.nch + blockIdx.x] = cost[0];
+}
+
+// (the workspace's control words and counts were zeroed before ba_init_kernel)
+__global__ __launch_bounds__(64) void ba_setup_kernel(BaArgs a) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    if (tid < a.V) {
+        const size_t v = (size_t)s * a.V + tid;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            double* p = a.pose + (((size_t)s * 2 + b) * a.V + tid) * 12;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) p[k] = a.Rs[v * 9 + k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[9 + k] = a.ts[v * 3 + k];
+        }
+    }
+    if (tid == 0) {
+        BaCtrl& c = a.ctrl[s];
+        unsigned fr = 0u;
+        for (int v = 0; v < a.V; ++v)
+            if (!((a.fixed >> v) & 1u) && a.counts[(size_t)s * 32 + v] >= ba::MIN_VIEW_OBS) fr |= 1u << v;
+        double cost = 0.0;
+        for (int j = 0; j < a.nch; ++j) cost = cost + a.partial[(size_t)s * a.nch + j];
+        c.free_views = (int32_t)fr;
+        c.cost0 = cost; c.cost = cost; c.lambda = ba::LAMBDA0;
+        c.status = (fr == 0u || c.n_refined == 0) ? ba::ST_NOTHING : (tv::is_finite(cost) ? ba::ST_OK : ba::ST_NOT_FINITE);
+        c.done = c.status != ba::ST_OK;
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_point_kernel(BaArgs a) {
+    __shared__ double vd[mv::MAX_VIEWS * ba::STRIDE];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const BaCtrl c = a.ctrl[s];
+    if (c.done) return;
+    ba_stage_state(a, s, c.cur, vd);
+    __syncthreads();
+    const int k = blockIdx.x * 256 + tid;
+    if (k >= a.K) return;
+    const size_t o = (size_t)s * a.K + k;
+    const unsigned M = a.mask[o];
+    if (!M) return;
+    const double* Xs = a.X + (((size_t)s * 2 + c.cur) * a.K + k) * 3;
+    const double X[3] = {Xs[0], Xs[1], Xs[2]};
+    double Vi[6], g[3];
+    const bool ok = ba_point(vd, ba_nv(a, s), ba_obs(a, o, s), M, X, a.huber, 1.0 + c.lambda, Vi, g);
+    double* pv = a.pv + o * 9;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) pv[j] = Vi[j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pv[6 + j] = g[j];
+    a.held[o] = ok ? 0 : 1;
+}
+
+// the term of track k in block (w, v): the pixel of a view through the table, as MvObs
+template <bool DIAG>
+__device__ inline void ba_schur_block(const BaArgs& a, int s, int v, int w, const BaCtrl& c, const double* pvw /* LDS: blocks of v and w */, double* red,
+                                      double* out, double* rhs) {
+    constexpr int N = DIAG ? 42 : 36;
+    const int tid = threadIdx.x;
+    double acc[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.0;
+    const double opl = 1.0 + c.lambda;
+    const unsigned need = (1u << v) | (1u << w);
+    const float* kp = a.kpts + (size_t)s * a.V * a.kcap * 2;
+    for (int k = tid; k < a.K; k += 256) {
+        const size_t o = (size_t)s * a.K + k;
+        if ((a.mask[o] & need) != need) continue;
+        const double* Xs = a.X + (((size_t)s * 2 + c.cur) * a.K + k) * 3;
+        const double X[3] = {Xs[0], Xs[1], Xs[2]};
+        const int32_t* row = a.tracks + o * a.V;
+        const float2 qv = *reinterpret_cast<const float2*>(kp + ((size_t)v * a.kcap + (unsigned)row[v]) * 2);
+        const double* pv = a.pv + o * 9;
+        const double Vi[6] = {pv[0], pv[1], pv[2], pv[3], pv[4], pv[5]}, g[3] = {pv[6], pv[7], pv[8]};
+        const bool held = a.held[o] != 0;
+        BaTerm tc;
+        ba_term(pvw, X, (double)qv.x, (double)qv.y, a.huber, tc);
+        if (DIAG) {
+            ba_pair_add<true>(tc, tc, Vi, g, held, opl, acc);
+        } else {
+            const float2 qw = *reinterpret_cast<const float2*>(kp + ((size_t)w * a.kcap + (unsigned)row[w]) * 2);
+            BaTerm tr;
+            ba_term(pvw + ba::STRIDE, X, (double)qw.x, (double)qw.y, a.huber, tr);
+            ba_pair_add<false>(tr, tc, Vi, g, held, opl, acc);
+        }
+    }
+    rs::block_sums(acc, red);
+    // entry (6 w + i, 6 v + j) of the packed triangle (the diagonal block: j <= i)
+#pragma unroll
+    for (int e = 0; e < 36; ++e) {
+        const int i = e / 6, j = e % 6;
+        if (tid == e && (!DIAG || j <= i)) out[(size_t)(6 * w + i) * (6 * w + i + 1) / 2 + 6 * v + j] = acc[e];
+    }
+    if (DIAG) {
+#pragma unroll
+        for (int e = 0; e < 6; ++e)
+            if (tid == 36 + e) rhs[6 * v + e] = acc[36 + e];
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_schur_kernel(BaArgs a) {
+    __shared__ double pvw[2 * ba::STRIDE];
+    __shared__ double red[rs::block_sums_bytes(42) / sizeof(double)];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const BaCtrl c = a.ctrl[s];
+    if (c.done) return;
+    int w = 0, rest = blockIdx.x;                          // pair index = w (w + 1) / 2 + v, v <= w
+    while (rest > w) { rest -= w + 1; ++w; }
+    const int v = rest;
+    const int n = 6 * a.V;
+    double* out = a.sys + (size_t)s * ((size_t)n * (n + 1) / 2 + n);
+    double* rhs = out + (size_t)n * (n + 1) / 2;
+    const unsigned fr = (unsigned)c.free_views;
+    if (!((fr >> v) & 1u) || !((fr >> w) & 1u)) {          // a held view: its rows are identity and zero
+        if (tid < 36) {
+            const int i = tid / 6, j = tid % 6;
+            if (v != w || j <= i) out[(size_t)(6 * w + i) * (6 * w + i + 1) / 2 + 6 * v + j] = (v == w && i == j) ? 1.0 : 0.0;
+        } else if (tid < 42 && v == w) {
+            rhs[6 * v + (tid - 36)] = 0.0;
+        }
+        return;
+    }
+    if (tid < 2) {
+        const int x = tid == 0 ? v : w;
+        const double* p = a.pose + (((size_t)s * 2 + c.cur) * a.V + x) * 12;
+        ba_stage_view(p, p + 9, a.Ks + ((size_t)s * a.V + x) * 9, pvw + tid * ba::STRIDE);
+    }
+    __syncthreads();
+    if (v == w) ba_schur_block<true>(a, s, v, w, c, pvw, red, out, rhs);
+    else ba_schur_block<false>(a, s, v, w, c, pvw, red, out, rhs);
+}
+
+struct BaBarrier {
+    __device__ inline void operator()() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(256) void ba_solve_kernel(BaArgs a) {
+    extern __shared__ double lds[];                        // the packed triangle, the right-hand side, the pivots
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const BaCtrl c = a.ctrl[s];
+    if (c.done) return;
+    const int n = 6 * a.V;
+    const size_t tri = (size_t)n * (n + 1) / 2;
+    double* L = lds;
+    double* r = lds + tri;
+    double* piv = r + n;
+    const double* src = a.sys + (size_t)s * (tri + n);
+    for (size_t i = tid; i < tri + n; i += 256) lds[i] = src[i];
+    const bool ok = ba_cholesky_solve(L, r, piv, n, tid, 256, BaBarrier());
+    if (!ok) {
+        if (tid == 0) a.ctrl[s].failed = 1;
+        return;
+    }
+    if (tid < n) a.dcam[(size_t)s * n + tid] = r[tid];
+    if (tid < a.V) {
+        const double* p = a.pose + (((size_t)s * 2 + c.cur) * a.V + tid) * 12;
+        double* q = a.pose + (((size_t)s * 2 + (1 - c.cur)) * a.V + tid) * 12;
+        double R[9], t[3], d6[6], Rn[9], tn[3];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = p[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = p[9 + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) d6[k] = r[6 * tid + k];
+        ba_pose_update(R, t, d6, Rn, tn);
+        const bool fr = ((unsigned)c.free_views >> tid) & 1u;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) q[k] = fr ? Rn[k] : R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q[9 + k] = fr ? tn[k] : t[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_update_kernel(BaArgs a) {
+    __shared__ double vd[mv::MAX_VIEWS * ba::STRIDE];      // the current poses
+    __shared__ double vc[mv::MAX_VIEWS * ba::STRIDE];      // the candidate poses
+    __shared__ double dc[6 * mv::MAX_VIEWS];
+    __shared__ double red[rs::block_sums_bytes(1) / sizeof(double)];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const BaCtrl c = a.ctrl[s];
+    if (c.done || c.failed) return;
+    const int n = 6 * a.V;
+    ba_stage_state(a, s, c.cur, vd);
+    ba_stage_state(a, s, 1 - c.cur, vc);
+    if (tid < n) dc[tid] = a.dcam[(size_t)s * n + tid];
+    __syncthreads();
+    const int k = blockIdx.x * 256 + tid;
+    double cost[1] = {0.0};
+    bool bad = false;
+    if (k < a.K) {
+        const size_t o = (size_t)s * a.K + k;
+        const unsigned M = a.mask[o];
+        if (M) {
+            const double* Xs = a.X + (((size_t)s * 2 + c.cur) * a.K + k) * 3;
+            double* Xc = a.X + (((size_t)s * 2 + (1 - c.cur)) * a.K + k) * 3;
+            const double X[3] = {Xs[0], Xs[1], Xs[2]};
+            const double* pv = a.pv + o * 9;
+            const double Vi[6] = {pv[0], pv[1], pv[2], pv[3], pv[4], pv[5]}, g[3] = {pv[6], pv[7], pv[8]};
+            const MvObs obs = ba_obs(a, o, s);
+            const int nv = ba_nv(a, s);
+            double Xn[3];
+            ba_point_step(vd, nv, obs, M, (unsigned)c.free_views, X, a.huber, Vi, g, a.held[o] != 0, dc, Xn);
+            Xc[0] = Xn[0]; Xc[1] = Xn[1]; Xc[2] = Xn[2];
+            cost[0] = ba_cost(vc, nv, obs, M, Xn, a.huber, bad);
+        }
+    }
+    const unsigned long long m = __ballot(bad);
+    if ((tid & 63) == 0 && m) atomicOr(&a.ctrl[s].bad, 1);
+    rs::block_sums(cost, red);
+    if (tid == 0) a.partial[(size_t)s * a.nch + blockIdx.x] = cost[0];
+}
+
+__global__ __launch_bounds__(64) void ba_decide_kernel(BaArgs a) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.S) return;
+    BaCtrl& c = a.ctrl[s];
+    if (c.done) return;
+    const bool failed = c.failed != 0 || c.bad != 0;
+    double cand = 0.0;
+    if (!failed)
+        for (int j = 0; j < a.nch; ++j) cand = cand + a.partial[(size_t)s * a.nch + j];
+    double lambda = c.lambda, cost = c.cost;
+    bool done;
+    const bool accept = ba_decide(failed, cand, lambda, cost, done);
+    c.lambda = lambda; c.cost = cost;
+    c.iters += 1;
+    if (accept) { c.accepted += 1; c.cur = 1 - c.cur; }
+    c.done = done ? 1 : 0;
+    c.failed = 0; c.bad = 0;
+}
+
+__global__ __launch_bounds__(256) void ba_final_kernel(BaArgs a) {
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const BaCtrl c = a.ctrl[s];
+    const int k = blockIdx.x * 256 + tid;
+    const bool ran = c.status == ba::ST_OK;
+    if (k < a.K) {
+        const size_t o = (size_t)s * a.K + k;
+        const bool ref = ran && a.mask[o] != 0u;
+        const double* Xs = a.X + (((size_t)s * 2 + c.cur) * a.K + k) * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float x = ref ? (float)Xs[j] : a.X0[3 * o + j];
+            a.Xout[3 * o + j] = x;
+        }
+        a.refined[o] = ref ? 1 : 0;
+    }
+    if (blockIdx.x != 0) return;
+    if (tid < a.V) {
+        const size_t v = (size_t)s * a.V + tid;
+        const double* p = a.pose + (((size_t)s * 2 + c.cur) * a.V + tid) * 12;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) a.Rout[v * 9 + j] = p[j];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a.tout[v * 3 + j] = p[9 + j];
+    }
+    if (tid == 0) {
+        a.free_out[s] = c.free_views;
+        a.cost_out[2 * s] = c.cost0; a.cost_out[2 * s + 1] = c.cost;
+        int nf = 0;
+        for (int v = 0; v < a.V; ++v) nf += (c.free_views >> v) & 1;
+        int32_t* info = a.info + (size_t)s * 8;
+        info[0] = ran ? c.n_refined : 0; info[1] = c.n_obs; info[2] = nf; info[3] = c.iters; info[4] = c.accepted; info[5] = c.status;
+        info[6] = 0; info[7] = 0;
+    }
+}
+
+static size_t ba_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// the workspace's parts in order: ctrl, counts, pose, X, mask, held, pv, sys, dcam, partial
+static size_t ba_layout(int S, int K, int V, size_t* off) {
+    const size_t n = 6 * (size_t)V, nch = (size_t)ceil_div(K, 256);
+    const size_t sz[10] = {(size_t)S * sizeof(BaCtrl), (size_t)S * 32 * 4, (size_t)S * 2 * V * 12 * 8, (size_t)S * 2 * K * 3 * 8, (size_t)S * K * 4,
+                           (size_t)S * K, (size_t)S * K * 9 * 8, (size_t)S * (n * (n + 1) / 2 + n) * 8, (size_t)S * n * 8, (size_t)S * nch * 8};
+    size_t at = 0;
+    for (int i = 0; i < 10; ++i) { if (off) off[i] = at; at += ba_align(sz[i]); }
+    return at;
+}
+size_t bundle_workspace_bytes(int S, int K, int V) { return ba_layout(S, K, V, nullptr); }
+
+int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, const int32_t* inlier_views, const float* points3d, const int32_t* n_views,
+                         int S, int K, int V, const double* Ks, const double* Rs, const double* ts, unsigned fixed_views, int max_iterations,
+                         double huber_px, double* Rs_out, double* ts_out, float* points3d_out, unsigned char* refined, int32_t* free_views, double* cost,
+                         int32_t* info, void* ws, hipStream_t st) {
+    if (S < 1 || S > 65535 || K < 1 || V < 2 || V > mv::MAX_VIEWS || kcap < 1 || max_iterations < 0) return -1;
+    size_t off[10];
+    ba_layout(S, K, V, off);
+    char* w = static_cast<char*>(ws);
+    BaArgs a = {};
+    a.kpts = kpts; a.tracks = tracks; a.inliers = inlier_views; a.X0 = points3d; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts;
+    a.S = S; a.K = K; a.V = V; a.kcap = kcap; a.nch = ceil_div(K, 256); a.fixed = fixed_views; a.huber = huber_px;
+    a.ctrl = reinterpret_cast<BaCtrl*>(w + off[0]); a.counts = reinterpret_cast<int32_t*>(w + off[1]); a.pose = reinterpret_cast<double*>(w + off[2]);
+    a.X = reinterpret_cast<double*>(w + off[3]); a.mask = reinterpret_cast<uint32_t*>(w + off[4]); a.held = reinterpret_cast<unsigned char*>(w + off[5]);
+    a.pv = reinterpret_cast<double*>(w + off[6]); a.sys = reinterpret_cast<double*>(w + off[7]); a.dcam = reinterpret_cast<double*>(w + off[8]);
+    a.partial = reinterpret_cast<double*>(w + off[9]);
+    a.Rout = Rs_out; a.tout = ts_out; a.Xout = points3d_out; a.refined = refined; a.free_out = free_views; a.cost_out = cost; a.info = info;
+    if (hipMemsetAsync(w, 0, off[2], st) != hipSuccess) return -1;                // the control words and the counts
+    const int n = 6 * V;
+    const int lds = (int)(((size_t)n * (n + 1) / 2 + 2 * (size_t)n) * sizeof(double));
+    static AttrMask attr_done{0};
+    set_max_dynamic_lds(reinterpret_cast<const void*>(ba_solve_kernel), 160 * 1024, attr_done);
+    const dim3 per_track(a.nch, S);
+    ba_init_kernel<<<per_track, 256, 0, st>>>(a);
+    ba_setup_kernel<<<S, 64, 0, st>>>(a);
+    for (int it = 0; it < max_iterations; ++it) {
+        ba_point_kernel<<<per_track, 256, 0, st>>>(a);
+        ba_schur_kernel<<<dim3(V * (V + 1) / 2, S), 256, 0, st>>>(a);
+        ba_solve_kernel<<<S, 256, lds, st>>>(a);
+        ba_update_kernel<<<per_track, 256, 0, st>>>(a);
+        ba_decide_kernel<<<ceil_div(S, 64), 64, 0, st>>>(a);
+    }
+    ba_final_kernel<<<per_track, 256, 0, st>>>(a);
+    return 0;
+}
+
 }  // namespace xfh

@@ -155,3 +155,98 @@ def triangulate_views_matches(kpts, idx_ref, idx_view, n_matches, n_views, Ks, R
     out = triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error, min_parallax_deg, max_depth, min_views)
     out['tracks'] = tracks
     return out
+
+
+# ---- bundle adjustment -----------------------------------------------------------------------------------------------------
+BA_STATUS = ("ok", "nothing_to_refine", "not_finite")       # info[:, 5]
+BA_INFO_FIELDS = ("refined_points", "observations", "free_views", "iterations", "accepted_steps", "status", "spare0", "spare1")
+MIN_VIEW_OBS = 6                             # ba::MIN_VIEW_OBS: a view with fewer observations is held
+MAX_BA_ITERATIONS = 1000
+WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of scenes
+
+
+def _ba_settings(who, fixed_views, max_iterations, huber_px):
+    if isinstance(fixed_views, bool) or not isinstance(fixed_views, int):
+        raise _lib.XFeatHipError(f"{who}: fixed_views must be an int bit mask of views")
+    if not 0 <= fixed_views < (1 << 32):
+        raise _lib.XFeatHipError(f"{who}: fixed_views {fixed_views} outside [0, 2^32)")
+    iters, c = int(max_iterations), float(huber_px)
+    if not 0 <= iters <= MAX_BA_ITERATIONS:
+        raise _lib.XFeatHipError(f"{who}: max_iterations {iters} outside [0, {MAX_BA_ITERATIONS}]")
+    if not c > 0.0:
+        raise _lib.XFeatHipError(f"{who}: huber_px {c} must be positive (inf: plain squares)")
+    return fixed_views, iters, c
+
+
+def bundle_adjust_batch(kpts, tracks, inlier_views, points3d, n_views, Ks, Rs, ts, fixed_views=1, max_iterations=10, huber_px=1.0):
+    """Bundle adjustment of S scenes in one call: the poses of the free views and the points of the valid tracks, refined together.
+
+    kpts, tracks, n_views, Ks, Rs, ts : as for ``triangulate_views_batch``;  inlier_views (S,K) int32 and points3d (S,K,3) float32: its result
+    fixed_views    : int bit mask of the views held constant (default 1: view 0; bit 0 need not be set)
+    max_iterations : Levenberg-Marquardt rounds at the most;  huber_px: the Huber loss's corner in pixels, inf = plain squares
+    The observations are fixed at the input state: (k, w) with bit w of inlier_views[k], w < n_views, a table entry in range, a finite pixel,
+    a usable pose, a finite point, depth > 0 and a finite error.  A track with fewer than 2 of them is not refined; a view is free when it is
+    not in fixed_views and keeps at least MIN_VIEW_OBS observations, every other view is held and still constrains the points.  Gauge: with
+    only view 0 held the global scale is free -- the damping keeps it where the start put it, nothing pins it; hold two views
+    (fixed_views=3) for a pinned gauge.
+    Returns a dict of CUDA tensors: 'Rs' (S,V,3,3), 'ts' (S,V,3) float64 (held views: the input's bits), 'points3d' (S,K,3) float32 (refined
+    tracks rounded once at the end, every other row the input's bits), 'refined' (S,K) bool, 'free_views' (S,) int32 mask, 'cost' (S,2)
+    float64 (the robust cost before and after), 'info' (S,8) int32 (BA_INFO_FIELDS; status: BA_STATUS).  Asynchronous."""
+    who = "bundle_adjust_batch"
+    fixed_views, iters, huber = _ba_settings(who, fixed_views, max_iterations, huber_px)
+    kpts, tracks = torch.as_tensor(kpts), torch.as_tensor(tracks)
+    inlier_views, points3d = torch.as_tensor(inlier_views), torch.as_tensor(points3d)
+    if kpts.dim() != 4 or kpts.shape[3] != 2 or tracks.dim() != 3 or tracks.shape[0] != kpts.shape[0] or tracks.shape[2] != kpts.shape[1]:
+        raise RuntimeError('expected kpts (S,V,Kcap,2) and tracks (S,K,V)')
+    S, V, kcap = kpts.shape[:3]
+    K = tracks.shape[1]
+    if inlier_views.shape != (S, K) or points3d.shape != (S, K, 3):
+        raise RuntimeError('expected inlier_views (S,K) and points3d (S,K,3)')
+    _views(who, V)
+    dev = kpts.device if kpts.is_cuda else _twoview.device("bundle adjustment")
+    kpts, tracks = kpts.to(dev).float().contiguous(), tracks.to(dev).to(torch.int32).contiguous()
+    inlier_views, points3d = inlier_views.to(dev).to(torch.int32).contiguous(), points3d.to(dev).float().contiguous()
+    if n_views is not None:
+        n_views = torch.as_tensor(n_views)
+        if n_views.shape != (S,):
+            raise RuntimeError('n_views must have one entry per scene')
+        n_views = n_views.to(dev).to(torch.int32).contiguous()
+    Ks, Rs, ts = _f64(Ks, (S, V, 3, 3), dev, 'Ks'), _f64(Rs, (S, V, 3, 3), dev, 'Rs'), _f64(ts, (S, V, 3), dev, 'ts')
+    if S == 0 or K == 0 or kcap == 0:         # no observation at all: nothing to refine
+        info = torch.zeros((S, 8), dtype=torch.int32, device=dev)
+        info[:, 5] = 1
+        return {'Rs': Rs.clone(), 'ts': ts.clone(), 'points3d': points3d.clone(), 'refined': torch.zeros((S, K), dtype=torch.bool, device=dev),
+                'free_views': torch.zeros((S,), dtype=torch.int32, device=dev), 'cost': torch.zeros((S, 2), dtype=torch.float64, device=dev),
+                'info': info}
+    Ro, to, Xo = torch.empty_like(Rs), torch.empty_like(ts), torch.empty_like(points3d)
+    refined = torch.empty((S, K), dtype=torch.uint8, device=dev)
+    free = torch.empty((S,), dtype=torch.int32, device=dev)
+    cost = torch.empty((S, 2), dtype=torch.float64, device=dev)
+    info = torch.empty((S, 8), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+
+    def call(a, b, ws, ws_bytes, stream):
+        return lib.xfh_bundle_adjust(_ptr(kpts[a:b]), kcap, _ptr(tracks[a:b]), _ptr(inlier_views[a:b]), _ptr(points3d[a:b]),
+                                     _ptr(n_views[a:b]) if n_views is not None else None, b - a, K, V, _ptr(Ks[a:b]), _ptr(Rs[a:b]), _ptr(ts[a:b]),
+                                     fixed_views, iters, huber, _ptr(Ro[a:b]), _ptr(to[a:b]), _ptr(Xo[a:b]), _ptr(refined[a:b]), _ptr(free[a:b]),
+                                     _ptr(cost[a:b]), _ptr(info[a:b]), ws, ws_bytes, stream)
+    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
+        _twoview.run_chunked("xfh_bundle_adjust", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_bundle_workspace_bytes(n, K, V), dev,
+                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    return {'Rs': Ro, 'ts': to, 'points3d': Xo, 'refined': refined.bool(), 'free_views': free, 'cost': cost, 'info': info}
+
+
+def refine_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=float('inf'), min_views=2,
+                       fixed_views=1, max_iterations=10, huber_px=1.0):
+    """``triangulate_views_batch`` -> ``bundle_adjust_batch`` -> ``triangulate_views_batch`` again under the refined poses, so the status and
+    the gates describe the refined map (the inlier views are selected anew; the points are the second triangulation's).  Returns the second
+    triangulation's dict ('points3d' feeds ``estimate_absolute_pose_matches`` as before) with 'Rs', 'ts' (the refined poses), 'refined',
+    'free_views', 'cost' and 'ba_info' of the adjustment added.  Asynchronous."""
+    who = "refine_views_batch"
+    _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    _ba_settings(who, fixed_views, max_iterations, huber_px)
+    first = triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    ba = bundle_adjust_batch(kpts, tracks, first['inlier_views'], first['points3d'], n_views, Ks, Rs, ts, fixed_views, max_iterations, huber_px)
+    out = triangulate_views_batch(kpts, tracks, n_views, Ks, ba['Rs'], ba['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views)
+    out.update(Rs=ba['Rs'], ts=ba['ts'], refined=ba['refined'], free_views=ba['free_views'], cost=ba['cost'], ba_info=ba['info'])
+    return out

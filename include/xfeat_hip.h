@@ -527,6 +527,31 @@ int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks,
                           int32_t* inlier_views, float* reproj_error, int32_t* info, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment: the poses of the free views and the points of the valid tracks of S scenes refined together by
+ * Levenberg-Marquardt on the Huber-robust reprojection error (DESIGN.md 3.17 / csrc/k_triangulate.hip).  Asynchronous; no host
+ * synchronisation inside.  Every argument check returns before any launch.
+ *   kpts, tracks, n_views, Ks, Rs, ts as for xfh_triangulate_views; inlier_views (S,K) int32 and points3d (S,K,3) fp32 are its
+ *   results.  Observation (k, w): bit w of inlier_views[k], w < n_views, an entry in range, a finite pixel, a usable pose, a
+ *   finite point, depth > 0 and a finite error at the input state.  A track with fewer than 2 observations is not refined; a
+ *   view is free when its bit in fixed_views is clear and it keeps at least 6 observations, every other view is held (its
+ *   observations still constrain the points).  With only one view held the global scale is free: damping keeps it near the
+ *   start, nothing pins it; hold two views for a pinned gauge.  max_iterations in [0, 1000]; huber_px > 0, +inf = plain squares.
+ *   Outputs: Rs_out (S,V,3,3), ts_out (S,V,3) fp64 (held views: the input's bits); points3d_out (S,K,3) fp32 (refined tracks
+ *   rounded once, every other row the input's bits); refined (S,K) uint8; free_views (S,) int32 mask; cost (S,2) fp64 = the
+ *   robust cost before and after; info (S,8) int32: refined points, observations, free views, iterations, accepted steps,
+ *   status (XFH_BA_*), 0, 0.  workspace: xfh_bundle_workspace_bytes(S, K, V) bytes, 256-byte aligned (0: bad shape).
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_BA_OK 0
+#define XFH_BA_NOTHING 1
+#define XFH_BA_NOT_FINITE 2
+size_t xfh_bundle_workspace_bytes(int S, int K, int V);
+int xfh_bundle_adjust(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* inlier_views, const float* points3d,
+                      const int32_t* n_views, int S, int K, int V, const double* Ks, const double* Rs, const double* ts,
+                      uint32_t fixed_views, int max_iterations, double huber_px, double* Rs_out, double* ts_out,
+                      float* points3d_out, uint8_t* refined, int32_t* free_views, double* cost, int32_t* info, void* workspace,
+                      size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
