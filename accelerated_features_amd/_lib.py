@@ -77,6 +77,9 @@ SIGNATURES = {
     "xfh_recover_pose_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
     "xfh_build_tracks": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "xfh_triangulate_views": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "xfh_triangulate_tracks": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "xfh_track_graph_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_build_tracks_graph": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_bundle_workspace_bytes": (_sz, [_i, _i, _i]),
     "xfh_bundle_adjust": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, C.c_uint32, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_fundamental_workspace_bytes": (_sz, [_i, _i]),

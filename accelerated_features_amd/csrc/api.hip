@@ -1187,6 +1187,52 @@ int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks,
     return check_launch(who);
 }
 
+int xfh_triangulate_tracks(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                           const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views,
+                           float* points3d, uint8_t* status, uint8_t* n_inliers, int32_t* inlier_views, float* reproj_error, int32_t* info,
+                           xfh_stream stream) {
+    const char* who = "xfh_triangulate_tracks";
+    if (!kpts || !tracks || !Ks || !Rs || !ts || !points3d || !status || !n_inliers || !inlier_views || !reproj_error || !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (K < 1 || K > (1 << 24) || kpt_cap < 1) return fail(XFH_ERR_ARG, "%s: bad shape (K %d, key-point capacity %d)", who, K, kpt_cap);
+    if (min_views < 2 || min_views > 32) return fail(XFH_ERR_ARG, "%s: min_views %d outside [2, 32]", who, min_views);
+    if (!(max_reproj_error > 0.0) || !std::isfinite(max_reproj_error))
+        return fail(XFH_ERR_ARG, "%s: max_reproj_error %g must be positive and finite", who, max_reproj_error);
+    if (!(max_depth > 0.0)) return fail(XFH_ERR_ARG, "%s: max_depth %g must be positive (+inf: no limit)", who, max_depth);
+    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return fail(XFH_ERR_ARG, "%s: cos_min %g outside [-1, 1]", who, cos_min);
+    if (launch_triangulate_tracks(kpts, kpt_cap, tracks, n_views, S, K, V, Ks, Rs, ts, max_reproj_error, cos_min, max_depth, min_views, points3d, status,
+                                  n_inliers, inlier_views, reproj_error, info, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
+// ---- key-point tracks over a graph of view pairs (k_tracks.hip): every check returns before any launch
+size_t xfh_track_graph_workspace_bytes(int S, int V, int K) {
+    if (S <= 0 || S > 65535 || V < 2 || V > 32 || K <= 0 || K > (1 << 24)) return 0;
+    return xfh::track_graph_workspace_bytes(S, V, K);
+}
+
+int xfh_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap,
+                           int V, int K, int min_length, int max_tracks, int32_t* tracks, int32_t* track_of, int32_t* n_tracks, int32_t* info,
+                           void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    const char* who = "xfh_build_tracks_graph";
+    if (!view_pairs || !idx_a || !idx_b || !n_matches || !tracks || !track_of || !n_tracks || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (P < 1 || P > 65535 || cap < 1 || cap > (1 << 24) || K < 1 || K > (1 << 24))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, K %d)", who, P, cap, K);
+    if (min_length < 2 || min_length > 32) return fail(XFH_ERR_ARG, "%s: min_length %d outside [2, 32]", who, min_length);
+    if (max_tracks < 1 || max_tracks > V * K) return fail(XFH_ERR_ARG, "%s: max_tracks %d outside [1, V K = %d]", who, max_tracks, V * K);
+    int rc = check_ws(workspace, workspace_bytes, xfh::track_graph_workspace_bytes(S, V, K));
+    if (rc) return rc;
+    if (launch_build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, S, P, cap, V, K, min_length, max_tracks, tracks, track_of, n_tracks, info,
+                                  workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
 // ---- bundle adjustment of poses and track points (k_triangulate.hip): every check returns before any launch
 size_t xfh_bundle_workspace_bytes(int S, int K, int V) {
     if (S <= 0 || S > 65535 || K <= 0 || K > (1 << 24) || V < 2 || V > 32) return 0;

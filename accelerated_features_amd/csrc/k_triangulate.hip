@@ -788,6 +788,207 @@ int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks,
 }
 
 // ================================================================================================================================================
+// Anchored triangulation of tracks that view 0 need not see (tests/tracks_reference.py restates it on multiview_reference's
+// functions and tests/test_tracks_emulated.py compiles the slice below, behind the two slices above, on the host).  mv_track_anchor is
+// mv_track with two changes: "view 0" is a = the lowest view of the observed set O, and status 1 is |O| < 2 alone.  Hypotheses of the pairs
+// (a, v), v in O, v > a ascending; MSAC over O; the inliers; a in I required (else status 5); the refit by mv_normal / mv_step; the gates
+// with the parallax against c_a.  Rrel, trel and E of the pair (a, v) are computed per hypothesis from the two staged view blocks in
+// mv_stage_view's operation order, so a track with a = 0 gets the bits of mv_track.  The per-view block keeps mv::STRIDE (mv_normal and
+// mv_reproj index with it); its RREL / TREL / ESS fields are not written and not read.
+//
+// Launch (no workspace): triangulate_tracks_kernel, thread = track, grid = (chunks of 256 of K, S), as triangulate_views_kernel.
+
+// ---- anchored solver begin (host-compilable: tests/test_tracks_emulated.py slices it out behind the two slices above) ----
+// the per-view block of view v without the fields of a fixed reference view: ROT, TRA, CAL, CEN, OK as mv_stage_view writes them
+__device__ inline void mva_stage_view(const double* Rv, const double* tv, const double* Kv, double* o) {
+    bool fin = true, rnz = false;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[mv::TRA + k] = tv[k]; fin = fin && tv::is_finite(tv[k]); }
+    o[mv::CAL] = Kv[0]; o[mv::CAL + 1] = Kv[4]; o[mv::CAL + 2] = Kv[2]; o[mv::CAL + 3] = Kv[5];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[mv::CEN + i] = -((Rv[i] * tv[0] + Rv[3 + i] * tv[1]) + Rv[6 + i] * tv[2]);
+    o[mv::OK] = fin && rnz ? 1.0 : 0.0;
+}
+// the per-track function; MvResult::winner is the view of the winning hypothesis
+template <class Obs>
+__device__ inline MvResult mv_track_anchor(const double* vd, int nv, const Obs& obs, double thr2, double cos_min, double max_depth, int min_views) {
+    const float nanv = __builtin_nanf("");
+    MvResult o;
+    o.X[0] = nanv; o.X[1] = nanv; o.X[2] = nanv; o.err = nanv;
+    o.status = mv::UNOBSERVED; o.n_inliers = 0; o.inliers = 0u; o.winner = -1; o.score = 0.0; o.cost0 = 0.0; o.cost1 = 0.0;
+    // ---- the observed set and its lowest view
+    unsigned O = 0u;
+    int nobs = 0, an = -1;
+    for (int w = 0; w < nv; ++w) {
+        double u, v;
+        const bool in = obs(w, u, v);
+        if (in && tv::is_finite(u) && tv::is_finite(v) && vd[w * mv::STRIDE + mv::OK] != 0.0) { O |= 1u << w; ++nobs; an = an < 0 ? w : an; }
+    }
+    if (nobs < 2) return o;
+    // ---- the hypotheses of the pairs (a, v)
+    const double* pa = vd + an * mv::STRIDE;
+    double ua, va;
+    obs(an, ua, va);
+    double Ra[9], ta[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Ra[k] = pa[mv::ROT + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ta[k] = pa[mv::TRA + k];
+    int first = -1;
+    double first_e2 = 0.0, best = 0.0, X[3] = {0.0, 0.0, 0.0};
+    for (int v = an + 1; v < nv; ++v) {
+        if (!((O >> v) & 1u)) continue;
+        const double* p = vd + v * mv::STRIDE;
+        double Rrel[9], trel[3], E[9], cal[8];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = (p[3 * i] * Ra[3 * j] + p[3 * i + 1] * Ra[3 * j + 1]) + p[3 * i + 2] * Ra[3 * j + 2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) trel[i] = p[mv::TRA + i] - ((Rrel[3 * i] * ta[0] + Rrel[3 * i + 1] * ta[1]) + Rrel[3 * i + 2] * ta[2]);
+        if (trel[0] == 0.0 && trel[1] == 0.0 && trel[2] == 0.0) continue;
+        tg_pose_E(Rrel, trel, E);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { cal[k] = pa[mv::CAL + k]; cal[4 + k] = p[mv::CAL + k]; }
+        double uv, vv;
+        obs(v, uv, vv);
+        const TgRays q = tg_correct(E, cal, ua, va, uv, vv);
+        double l0, l1, zz, r[3], Xc[3];
+        tg_depths(Rrel, trel, q, l0, l1, zz, r);
+        const int st = tg_depth_status(true, q, l0, l1, zz, max_depth, Xc);
+        if (first < 0) { first = st; first_e2 = q.e2; }
+        if (st != tg::VALID) continue;
+        const double d[3] = {Xc[0] - ta[0], Xc[1] - ta[1], Xc[2] - ta[2]};
+        double Xw[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Xw[i] = (Ra[i] * d[0] + Ra[3 + i] * d[1]) + Ra[6 + i] * d[2];
+        double sc = 0.0;
+        for (int w = an; w < nv; ++w) {
+            if (!((O >> w) & 1u)) continue;
+            double u, vpx, z;
+            obs(w, u, vpx);
+            const double e2 = mv_reproj(vd + w * mv::STRIDE, Xw, u, vpx, z);
+            sc = sc + (z > 0.0 && tv::is_finite(e2) && e2 < thr2 ? e2 : thr2);
+        }
+        if (o.winner < 0 || sc < best) { o.winner = v; best = sc; X[0] = Xw[0]; X[1] = Xw[1]; X[2] = Xw[2]; }
+    }
+    if (o.winner < 0) {
+        o.status = first < 0 ? tg::NOT_FINITE : first;
+        if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(first_e2);
+        return o;
+    }
+    o.score = best;
+    // ---- the inliers of the winner
+    unsigned I = 0u;
+    int ni = 0;
+    double emax = 0.0;
+    for (int w = an; w < nv; ++w) {
+        if (!((O >> w) & 1u)) continue;
+        double u, vpx, z;
+        obs(w, u, vpx);
+        const double e2 = mv_reproj(vd + w * mv::STRIDE, X, u, vpx, z);
+        if (z > 0.0 && e2 <= thr2) { I |= 1u << w; ++ni; emax = e2 > emax ? e2 : emax; }
+    }
+    o.inliers = I; o.n_inliers = ni;
+    if (!((I >> an) & 1u) || ni < min_views) { o.status = tg::REPROJ; o.err = (float)sqrt(emax); return o; }
+    // ---- the refit on the fixed inlier set
+    double A[6], g[3];
+    double cost = mv_normal(vd, nv, obs, I, X, A, g);
+    o.cost0 = cost;
+    for (int it = 0; it < mv::GN_ITERS; ++it) {
+        double d[3], An[6], gn[3];
+        mv_step(A, g, d);
+        const double Xn[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
+        const double cn = mv_normal(vd, nv, obs, I, Xn, An, gn);
+        if (!(cn < cost)) break;
+        cost = cn; X[0] = Xn[0]; X[1] = Xn[1]; X[2] = Xn[2];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) A[k] = An[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k] = gn[k];
+    }
+    o.cost1 = cost;
+    // ---- the final gates
+    bool fin = tv::is_finite(X[0]) && tv::is_finite(X[1]) && tv::is_finite(X[2]), behind = false, far = false;
+    double cmin = 2.0;
+    emax = 0.0;
+    const double a[3] = {X[0] - pa[mv::CEN], X[1] - pa[mv::CEN + 1], X[2] - pa[mv::CEN + 2]};
+    const double aa = tv::dot3(a, a);
+    for (int w = an; w < nv; ++w) {
+        if (!((I >> w) & 1u)) continue;
+        const double* p = vd + w * mv::STRIDE;
+        double u, vpx, z;
+        obs(w, u, vpx);
+        const double e2 = mv_reproj(p, X, u, vpx, z);
+        fin = fin && tv::is_finite(e2) && tv::is_finite(z);
+        behind = behind || !(z > 0.0);
+        far = far || z > max_depth;
+        emax = e2 > emax ? e2 : emax;
+        if (w > an) {
+            const double b[3] = {X[0] - p[mv::CEN], X[1] - p[mv::CEN + 1], X[2] - p[mv::CEN + 2]};
+            const double c = tv::dot3(a, b) / sqrt(aa * tv::dot3(b, b));
+            cmin = c < cmin ? c : cmin;
+        }
+    }
+    o.status = !fin ? tg::NOT_FINITE : (behind ? tg::BEHIND : (far ? tg::FAR : (emax > thr2 ? tg::REPROJ : (cmin > cos_min ? tg::PARALLAX : tg::VALID))));
+    if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(emax);
+    if (o.status == tg::VALID) { o.X[0] = (float)X[0]; o.X[1] = (float)X[1]; o.X[2] = (float)X[2]; }
+    return o;
+}
+// ---- anchored solver end ----
+
+__global__ __launch_bounds__(256) void triangulate_tracks_kernel(MvArgs a) {
+    __shared__ double vd[mv::MAX_VIEWS * mv::STRIDE];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const int k = blockIdx.x * 256 + tid;
+    int nv = a.n_views ? a.n_views[s] : a.V;
+    nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
+    if (tid < a.V) {
+        const size_t v = (size_t)s * a.V + tid;
+        mva_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * mv::STRIDE);
+    }
+    __syncthreads();
+    const bool counted = k < a.K;
+    int st = -1;
+    if (counted) {
+        const size_t o = (size_t)s * a.K + k;
+        MvObs obs;
+        obs.row = a.tracks + o * a.V; obs.kp = a.kpts + (size_t)s * a.V * a.kcap * 2; obs.kcap = (unsigned)a.kcap;
+        const MvResult r = mv_track_anchor(vd, nv, obs, a.thr2, a.cos_min, a.max_depth, a.min_views);
+        st = r.status;
+        a.X[3 * o] = r.X[0]; a.X[3 * o + 1] = r.X[1]; a.X[3 * o + 2] = r.X[2];
+        a.status[o] = (unsigned char)st;
+        a.n_inliers[o] = (unsigned char)r.n_inliers;
+        a.inliers[o] = (int32_t)r.inliers;
+        a.err[o] = r.err;
+    }
+    // ---- status counts: one ballot per status, one atomic per wave and status
+    int32_t* info = a.info + (size_t)s * 8;
+    const bool lead = (tid & 63) == 0;
+#pragma unroll
+    for (int c = 0; c < tg::NSTATUS; ++c) {
+        const unsigned long long m = __ballot(counted && st == c);
+        if (lead && m) atomicAdd(info + 1 + c, (int)__popcll(m));
+    }
+    if (blockIdx.x == 0 && tid == 0) info[0] = a.K;        // (the counts were zeroed before the launch; nobody adds to word 0)
+}
+
+int launch_triangulate_tracks(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
+                              unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st) {
+    if (S < 1 || S > 65535 || K < 1 || V < 2 || V > mv::MAX_VIEWS || kcap < 1) return -1;
+    MvArgs a = {};
+    a.kpts = kpts; a.tracks = tracks; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts; a.K = K; a.V = V; a.kcap = kcap; a.min_views = min_views;
+    a.thr2 = max_reproj_error * max_reproj_error; a.cos_min = cos_min; a.max_depth = max_depth;
+    a.X = X; a.status = status; a.n_inliers = n_inliers; a.inliers = inliers; a.err = err; a.info = info;
+    if (hipMemsetAsync(info, 0, (size_t)S * 8 * sizeof(int32_t), st) != hipSuccess) return -1;
+    triangulate_tracks_kernel<<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
+    return 0;
+}
+
+// ================================================================================================================================================
 // Bundle adjustment of the poses of the free views and the points of the valid tracks (tests/bundle_reference.py restates it
 // operation for operation and tests/test_bundle_emulated.py compiles the slice below, behind the two slices above, on the host and holds it
 // to that restatement bit for bit).  Levenberg-Marquardt with Marquardt scaling on sum rho(e_w), e_w^2 = mv_reproj's, rho = Huber's at c pixels:

@@ -136,12 +136,21 @@ int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const i
 int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
                              unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st);
+// (the same for tracks that view 0 need not see: the anchor of a track is the lowest view that observes it)
+int launch_triangulate_tracks(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
+                              unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st);
 // (bundle adjustment of the poses of the free views and the points of the valid tracks: Levenberg-Marquardt through the Schur complement)
 size_t bundle_workspace_bytes(int S, int K, int V);
 int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, const int32_t* inlier_views, const float* points3d, const int32_t* n_views,
                          int S, int K, int V, const double* Ks, const double* Rs, const double* ts, unsigned fixed_views, int max_iterations,
                          double huber_px, double* Rs_out, double* ts_out, float* points3d_out, unsigned char* refined, int32_t* free_views, double* cost,
                          int32_t* info, void* ws, hipStream_t st);
+// ---- k_tracks.hip (key-point tracks over a graph of view pairs: connected components of the match graph by a lock-free union-find) ----
+size_t track_graph_workspace_bytes(int S, int V, int K);
+int launch_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap, int V,
+                              int K, int min_length, int max_tracks, int32_t* tracks, int32_t* track_of, int32_t* n_tracks, int32_t* info, void* ws,
+                              hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

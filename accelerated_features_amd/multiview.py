@@ -9,6 +9,11 @@ come out in the world frame, at the reference view's key-point rows: ``points3d_
 image, so "map from k views -> localise view k + 1 -> extend the map" never leaves HBM.  The kernels behind ``xfh_build_tracks`` /
 ``xfh_triangulate_views`` (include/xfeat_hip.h, csrc/k_triangulate.hip) are specified in DESIGN.md 3.16.  There is no CPU path: without the
 HIP library and a gfx950 device the functions raise.
+
+With the matches of arbitrary pairs of views (a sequence's (v, v + 1), an unordered set) ``build_tracks_graph`` makes the tables from the
+connected components of the match graph, ``triangulate_views_batch(anchor='first')`` triangulates each track from its lowest observing
+view, ``triangulate_graph_matches`` does both and ``view_points`` hands the map to ``estimate_absolute_pose_matches`` at any view's rows
+(``xfh_build_tracks_graph`` / ``xfh_triangulate_tracks``, csrc/k_tracks.hip).
 """
 import math
 
@@ -88,7 +93,17 @@ def _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views):
     return thr, math.cos(math.radians(deg)), depth, int(min_views)
 
 
-def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=float('inf'), min_views=2):
+ANCHORS = {'reference': 'xfh_triangulate_views', 'first': 'xfh_triangulate_tracks'}
+
+
+def _anchor(who, anchor):
+    if anchor not in ANCHORS:
+        raise _lib.XFeatHipError(f"{who}: anchor {anchor!r} is neither 'reference' nor 'first'")
+    return ANCHORS[anchor]
+
+
+def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=float('inf'), min_views=2,
+                            anchor='reference'):
     """The 3D points of the tracks of S scenes from all the views that see them, in one call.
 
     kpts    : (S, V, Kcap, 2) float32 pixel coordinates, the key-point tables of the V <= 32 views; view 0 is the reference view
@@ -104,9 +119,12 @@ def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=
     Returns a dict of CUDA tensors: 'points3d' (S,K,3) float32 in the world frame, NaN unless valid (``points3d_ref`` of
     ``estimate_absolute_pose_matches`` as it is, with its ``idx_ref`` the reference rows), 'status' (S,K) uint8, 'n_inliers' (S,K) uint8,
     'inlier_views' (S,K) int32 (bit v = view v), 'reproj_error' (S,K) float32 pixels (the largest inlier error; NaN for status 1 and 2),
-    'info' (S,8) int32 (INFO_FIELDS: K and the number of tracks per status), 'valid' (S,K) bool.  Asynchronous."""
+    'info' (S,8) int32 (INFO_FIELDS: K and the number of tracks per status), 'valid' (S,K) bool.  Asynchronous.
+    anchor='first' (the tables of ``build_tracks_graph``): "view 0" above is the lowest view that observes the track, status 1
+    is fewer than two observing views alone; a track whose lowest observing view is 0 gets the same bits either way."""
     who = "triangulate_views_batch"
     thr, cos_min, depth, min_views = _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    entry = _anchor(who, anchor)
     kpts, tracks = torch.as_tensor(kpts), torch.as_tensor(tracks)
     if kpts.dim() != 4 or kpts.shape[3] != 2 or tracks.dim() != 3 or tracks.shape[0] != kpts.shape[0] or tracks.shape[2] != kpts.shape[1]:
         raise RuntimeError('expected kpts (S,V,Kcap,2) and tracks (S,K,V)')
@@ -136,9 +154,9 @@ def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=
         lib = _lib.load()
         stream = torch.cuda.current_stream(dev).cuda_stream
         for a, b in _chunks(S):
-            _lib.check(lib.xfh_triangulate_views(_ptr(kpts[a:b]), kcap, _ptr(tracks[a:b]), _ptr(n_views[a:b]) if n_views is not None else None, b - a, K, V,
-                                                 _ptr(Ks[a:b]), _ptr(Rs[a:b]), _ptr(ts[a:b]), thr, cos_min, depth, min_views, _ptr(X[a:b]), _ptr(status[a:b]),
-                                                 _ptr(ninl[a:b]), _ptr(inl[a:b]), _ptr(err[a:b]), _ptr(info[a:b]), stream), "xfh_triangulate_views")
+            _lib.check(getattr(lib, entry)(_ptr(kpts[a:b]), kcap, _ptr(tracks[a:b]), _ptr(n_views[a:b]) if n_views is not None else None, b - a, K, V,
+                                           _ptr(Ks[a:b]), _ptr(Rs[a:b]), _ptr(ts[a:b]), thr, cos_min, depth, min_views, _ptr(X[a:b]), _ptr(status[a:b]),
+                                           _ptr(ninl[a:b]), _ptr(inl[a:b]), _ptr(err[a:b]), _ptr(info[a:b]), stream), entry)
     return {'points3d': X, 'status': status, 'n_inliers': ninl, 'inlier_views': inl, 'reproj_error': err, 'info': info, 'valid': status == 0}
 
 
@@ -237,16 +255,121 @@ def bundle_adjust_batch(kpts, tracks, inlier_views, points3d, n_views, Ks, Rs, t
 
 
 def refine_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=float('inf'), min_views=2,
-                       fixed_views=1, max_iterations=10, huber_px=1.0):
+                       fixed_views=1, max_iterations=10, huber_px=1.0, anchor='reference'):
     """``triangulate_views_batch`` -> ``bundle_adjust_batch`` -> ``triangulate_views_batch`` again under the refined poses, so the status and
     the gates describe the refined map (the inlier views are selected anew; the points are the second triangulation's).  Returns the second
     triangulation's dict ('points3d' feeds ``estimate_absolute_pose_matches`` as before) with 'Rs', 'ts' (the refined poses), 'refined',
-    'free_views', 'cost' and 'ba_info' of the adjustment added.  Asynchronous."""
+    'free_views', 'cost' and 'ba_info' of the adjustment added.  anchor: of both triangulations.  Asynchronous."""
     who = "refine_views_batch"
     _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
     _ba_settings(who, fixed_views, max_iterations, huber_px)
-    first = triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    _anchor(who, anchor)
+    first = triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error, min_parallax_deg, max_depth, min_views, anchor)
     ba = bundle_adjust_batch(kpts, tracks, first['inlier_views'], first['points3d'], n_views, Ks, Rs, ts, fixed_views, max_iterations, huber_px)
-    out = triangulate_views_batch(kpts, tracks, n_views, Ks, ba['Rs'], ba['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views)
+    out = triangulate_views_batch(kpts, tracks, n_views, Ks, ba['Rs'], ba['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views, anchor)
     out.update(Rs=ba['Rs'], ts=ba['ts'], refined=ba['refined'], free_views=ba['free_views'], cost=ba['cost'], ba_info=ba['info'])
+    return out
+
+
+# ---- tracks over a graph of view pairs (DESIGN.md 3.18) ---------------------------------------------------------------------------------------
+TRACK_STATUS = ("ok", "unused", "bound_reached")           # track_info[:, 6]
+TRACK_INFO_FIELDS = ("nodes", "components", "tracks", "inconsistent", "short", "over_capacity", "status", "spare")
+MAX_PAIRS = 65535
+
+
+def build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, n_views, K, min_length=2, max_tracks=None):
+    """The track tables of S scenes from the matcher's lists of any pairs of views: the connected components of the match graph.
+
+    view_pairs   : (S, P, 2) or (P, 2) int32: pair p matches view view_pairs[..., p, 0] against view view_pairs[..., p, 1]
+    idx_a, idx_b : (S, P, cap) int64 CUDA tensors: match i of pair p = (a, b) is (row idx_a[s, p, i] of view a, row idx_b[s, p, i] of view b)
+                   for i < n_matches[s, p];  n_matches (S, P) int32;  n_views: V <= 32;  K: rows of the key-point tables
+    A pair with a == b or a view outside [0, V) and an index outside [0, K) are ignored; a pair may occur more than once.  A track is a
+    component with at most one key-point per view (any other component is dropped whole) that spans at least min_length views.  Its id is
+    the rank of its smallest node (lowest view, then row) within the scene; ids from max_tracks (None: (V K) // 2, more cannot exist) on are
+    dropped and counted.  The tables do not depend on the order of the lists: two calls give the same bytes.
+    Returns (tracks (S, T, V) int32: a row or -1, rows >= n_tracks[s] all -1;  track_of (S, V, K) int32: the track of a key-point or -1;
+    n_tracks (S,) int32;  info (S, 8) int32: TRACK_INFO_FIELDS, status: TRACK_STATUS).  Asynchronous."""
+    who = "build_tracks_graph"
+    for t in (view_pairs, idx_a, idx_b, n_matches):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f'{who}: tensors expected')
+    V, K = int(n_views), int(K)
+    if K < 0:
+        raise RuntimeError(f'{who}: K {K} is negative')
+    _views(who, V)
+    if idx_a.dim() != 3 or idx_b.shape != idx_a.shape or n_matches.shape != idx_a.shape[:2]:
+        raise RuntimeError('expected idx_a, idx_b (S,P,cap) and n_matches (S,P)')
+    S, P, cap = idx_a.shape
+    if view_pairs.shape not in ((S, P, 2), (P, 2)):
+        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    if P > MAX_PAIRS:
+        raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_PAIRS}")
+    if not 2 <= int(min_length) <= MAX_VIEWS:
+        raise _lib.XFeatHipError(f"{who}: min_length {min_length} outside [2, {MAX_VIEWS}]")
+    T = (V * K) // 2 if max_tracks is None else int(max_tracks)
+    if max_tracks is not None and not 1 <= T <= max(V * K, 1):
+        raise _lib.XFeatHipError(f"{who}: max_tracks {T} outside [1, V K = {V * K}]")
+    if not idx_a.is_cuda:
+        raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
+    for t, dt in ((view_pairs, torch.int32), (idx_a, torch.int64), (idx_b, torch.int64), (n_matches, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != idx_a.device:
+            raise RuntimeError(f'{who}: contiguous int32 pairs, int64 indices and int32 counts on one device expected')
+    dev = idx_a.device
+    if view_pairs.dim() == 2:
+        view_pairs = view_pairs.expand(S, P, 2).contiguous()
+    tracks = torch.empty((S, T, V), dtype=torch.int32, device=dev)
+    track_of = torch.empty((S, V, K), dtype=torch.int32, device=dev)
+    n_tracks = torch.empty((S,), dtype=torch.int32, device=dev)
+    info = torch.empty((S, 8), dtype=torch.int32, device=dev)
+    if S == 0 or K == 0 or P == 0 or cap == 0:                # no match at all: written like the kernels write it
+        tracks.fill_(-1); track_of.fill_(-1); n_tracks.zero_(); info.zero_()
+        return tracks, track_of, n_tracks, info
+    lib = _lib.load()
+
+    def call(a, b, ws, ws_bytes, stream):
+        return lib.xfh_build_tracks_graph(_ptr(view_pairs[a:b]), _ptr(idx_a[a:b]), _ptr(idx_b[a:b]), _ptr(n_matches[a:b]), b - a, P, cap, V, K,
+                                          int(min_length), T, _ptr(tracks[a:b]), _ptr(track_of[a:b]), _ptr(n_tracks[a:b]), _ptr(info[a:b]), ws,
+                                          ws_bytes, stream)
+    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
+        _twoview.run_chunked("xfh_build_tracks_graph", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_track_graph_workspace_bytes(n, V, K), dev,
+                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    return tracks, track_of, n_tracks, info
+
+
+def triangulate_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0,
+                              max_depth=float('inf'), min_views=2, min_length=2, max_tracks=None):
+    """``build_tracks_graph`` on the matcher's lists of any pairs of views, then ``triangulate_views_batch(anchor='first')`` on its table:
+    kpts (S,V,K,2), view_pairs (S,P,2) or (P,2) int32, idx_a / idx_b (S,P,cap) int64, n_matches (S,P) int32 CUDA tensors; n_views (S,) int32
+    or None as for ``triangulate_views_batch`` (the tracks are built over all V views).  The result dict of the triangulation over the T
+    rows of the table (rows >= n_tracks are unobserved), with 'tracks' (S,T,V), 'track_of' (S,V,K), 'n_tracks' (S,) and 'track_info' (S,8)
+    added."""
+    who = "triangulate_graph_matches"
+    _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    if not torch.is_tensor(kpts) or kpts.dim() != 4 or kpts.shape[3] != 2:
+        raise RuntimeError('expected kpts (S,V,K,2)')
+    if torch.is_tensor(idx_a) and idx_a.dim() == 3 and idx_a.shape[0] != kpts.shape[0]:
+        raise RuntimeError('expected idx_a, idx_b (S,P,cap) for kpts (S,V,K,2)')
+    tracks, track_of, n_tracks, info = build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, kpts.shape[1], kpts.shape[2], min_length, max_tracks)
+    out = triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error, min_parallax_deg, max_depth, min_views, anchor='first')
+    out.update(tracks=tracks, track_of=track_of, n_tracks=n_tracks, track_info=info)
+    return out
+
+
+def view_points(points3d, track_of, view):
+    """The points of the tracks at the key-point rows of one view: points3d (S,T,3) float32 and track_of (S,V,K) int32 of
+    ``triangulate_graph_matches`` -> (S,K,3) float32, NaN where the key-point has no track (or its track no point).  It is
+    ``points3d_ref`` of ``estimate_absolute_pose_matches`` for an image matched against that view."""
+    points3d, track_of = torch.as_tensor(points3d), torch.as_tensor(track_of)
+    if points3d.dim() != 3 or points3d.shape[2] != 3 or track_of.dim() != 3 or track_of.shape[0] != points3d.shape[0]:
+        raise RuntimeError('expected points3d (S,T,3) and track_of (S,V,K)')
+    view = int(view)
+    if not 0 <= view < track_of.shape[1]:
+        raise RuntimeError(f'view {view} outside [0, {track_of.shape[1]})')
+    t = track_of[:, view].to(points3d.device).long()
+    T = points3d.shape[1]
+    has = (t >= 0) & (t < T)
+    out = torch.full(t.shape + (3,), float('nan'), dtype=torch.float32, device=points3d.device)
+    if T:
+        got = torch.gather(points3d.float(), 1, t.clamp(0, T - 1).unsqueeze(-1).expand(-1, -1, 3))
+        out = torch.where(has.unsqueeze(-1), got, out)
     return out

@@ -527,6 +527,36 @@ int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks,
                           int32_t* inlier_views, float* reproj_error, int32_t* info, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracks over an arbitrary graph of view pairs, and their triangulation (DESIGN.md 3.18 / csrc/k_tracks.hip,
+ * csrc/k_triangulate.hip).  Every argument check returns before any launch; asynchronous, no host synchronisation inside.
+ *   xfh_build_tracks_graph: view_pairs (S,P,2) int32, idx_a, idx_b (S,P,cap) int64, n_matches (S,P) int32: match i of pair
+ *     p = (a, b) joins row idx_a[i] of view a with row idx_b[i] of view b (tables of K rows, V <= 32 views).  A pair with
+ *     a == b or a view outside [0, V) and an index outside [0, K) are ignored; a pair may occur more than once.  A track is a
+ *     connected component of the match graph with at most one key-point per view (others are dropped whole) that spans at
+ *     least min_length (in [2, 32]) views; its id is the rank of its smallest node id v K + row within the scene; ids at or
+ *     beyond max_tracks (in [1, V K]) are dropped and counted.  The result does not depend on the order of the lists.
+ *     tracks (S,max_tracks,V) int32: a row or -1, rows >= n_tracks[s] all -1; track_of (S,V,K) int32: the track of a
+ *     key-point or -1; n_tracks (S,) int32; info (S,8) int32: nodes matched, components, tracks kept, dropped inconsistent,
+ *     dropped short, dropped over capacity, status (XFH_TRACKS_*), 0.  Every loop of the kernels is bounded by V K; status
+ *     XFH_TRACKS_BOUND says that a thread reached its bound and gave up (the tables are then not to be used).
+ *     workspace: xfh_track_graph_workspace_bytes(S, V, K) bytes, 256-byte aligned (0: bad shape).
+ *   xfh_triangulate_tracks: the arguments and outputs of xfh_triangulate_views for tracks that view 0 need not see.  The
+ *     anchor of a track is the lowest view that observes it: hypotheses of the pairs (anchor, v), status XFH_MV_UNOBSERVED
+ *     only with fewer than two observing views, the anchor among the inliers or status 5, parallax against the anchor.  A
+ *     track whose anchor is view 0 gets the bits of xfh_triangulate_views.
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_TRACKS_OK 0
+#define XFH_TRACKS_BOUND 2
+size_t xfh_track_graph_workspace_bytes(int S, int V, int K);
+int xfh_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S,
+                           int P, int cap, int V, int K, int min_length, int max_tracks, int32_t* tracks, int32_t* track_of,
+                           int32_t* n_tracks, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_triangulate_tracks(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V,
+                           const double* Ks, const double* Rs, const double* ts, double max_reproj_error, double cos_min,
+                           double max_depth, int min_views, float* points3d, uint8_t* status, uint8_t* n_inliers,
+                           int32_t* inlier_views, float* reproj_error, int32_t* info, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bundle adjustment: the poses of the free views and the points of the valid tracks of S scenes refined together by
  * Levenberg-Marquardt on the Huber-robust reprojection error (DESIGN.md 3.17 / csrc/k_triangulate.hip).  Asynchronous; no host
  * synchronisation inside.  Every argument check returns before any launch.
