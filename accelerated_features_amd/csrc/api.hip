@@ -1166,11 +1166,11 @@ int xfh_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int3
     return check_launch(who);
 }
 
-int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
-                          const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views,
-                          float* points3d, uint8_t* status, uint8_t* n_inliers, int32_t* inlier_views, float* reproj_error, int32_t* info,
-                          xfh_stream stream) {
-    const char* who = "xfh_triangulate_views";
+// (first: the anchor of a track is the lowest view that observes it, not view 0)
+static int triangulate_views_impl(const char* who, bool first, const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S,
+                                  int K, int V, const double* Ks, const double* Rs, const double* ts, double max_reproj_error, double cos_min,
+                                  double max_depth, int min_views, float* points3d, uint8_t* status, uint8_t* n_inliers, int32_t* inlier_views,
+                                  float* reproj_error, int32_t* info, xfh_stream stream) {
     if (!kpts || !tracks || !Ks || !Rs || !ts || !points3d || !status || !n_inliers || !inlier_views || !reproj_error || !info)
         return fail(XFH_ERR_ARG, "%s: NULL argument", who);
     if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
@@ -1182,30 +1182,25 @@ int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks,
     if (!(max_depth > 0.0)) return fail(XFH_ERR_ARG, "%s: max_depth %g must be positive (+inf: no limit)", who, max_depth);
     if (!(cos_min >= -1.0 && cos_min <= 1.0)) return fail(XFH_ERR_ARG, "%s: cos_min %g outside [-1, 1]", who, cos_min);
     if (launch_triangulate_views(kpts, kpt_cap, tracks, n_views, S, K, V, Ks, Rs, ts, max_reproj_error, cos_min, max_depth, min_views, points3d, status,
-                                 n_inliers, inlier_views, reproj_error, info, (hipStream_t)stream))
+                                 n_inliers, inlier_views, reproj_error, info, first, (hipStream_t)stream))
         return fail(XFH_ERR_HIP, "%s: the launch failed", who);
     return check_launch(who);
+}
+
+int xfh_triangulate_views(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                          const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views,
+                          float* points3d, uint8_t* status, uint8_t* n_inliers, int32_t* inlier_views, float* reproj_error, int32_t* info,
+                          xfh_stream stream) {
+    return triangulate_views_impl("xfh_triangulate_views", false, kpts, kpt_cap, tracks, n_views, S, K, V, Ks, Rs, ts, max_reproj_error, cos_min,
+                                  max_depth, min_views, points3d, status, n_inliers, inlier_views, reproj_error, info, stream);
 }
 
 int xfh_triangulate_tracks(const float* kpts, int kpt_cap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
                            const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views,
                            float* points3d, uint8_t* status, uint8_t* n_inliers, int32_t* inlier_views, float* reproj_error, int32_t* info,
                            xfh_stream stream) {
-    const char* who = "xfh_triangulate_tracks";
-    if (!kpts || !tracks || !Ks || !Rs || !ts || !points3d || !status || !n_inliers || !inlier_views || !reproj_error || !info)
-        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
-    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
-    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
-    if (K < 1 || K > (1 << 24) || kpt_cap < 1) return fail(XFH_ERR_ARG, "%s: bad shape (K %d, key-point capacity %d)", who, K, kpt_cap);
-    if (min_views < 2 || min_views > 32) return fail(XFH_ERR_ARG, "%s: min_views %d outside [2, 32]", who, min_views);
-    if (!(max_reproj_error > 0.0) || !std::isfinite(max_reproj_error))
-        return fail(XFH_ERR_ARG, "%s: max_reproj_error %g must be positive and finite", who, max_reproj_error);
-    if (!(max_depth > 0.0)) return fail(XFH_ERR_ARG, "%s: max_depth %g must be positive (+inf: no limit)", who, max_depth);
-    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return fail(XFH_ERR_ARG, "%s: cos_min %g outside [-1, 1]", who, cos_min);
-    if (launch_triangulate_tracks(kpts, kpt_cap, tracks, n_views, S, K, V, Ks, Rs, ts, max_reproj_error, cos_min, max_depth, min_views, points3d, status,
-                                  n_inliers, inlier_views, reproj_error, info, (hipStream_t)stream))
-        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
-    return check_launch(who);
+    return triangulate_views_impl("xfh_triangulate_tracks", true, kpts, kpt_cap, tracks, n_views, S, K, V, Ks, Rs, ts, max_reproj_error, cos_min,
+                                  max_depth, min_views, points3d, status, n_inliers, inlier_views, reproj_error, info, stream);
 }
 
 // ---- key-point tracks over a graph of view pairs (k_tracks.hip): every check returns before any launch

@@ -444,35 +444,43 @@ int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, c
 }
 
 // ================================================================================================================================================
-// Multi-view triangulation of key-point tracks (tests/multiview_reference.py restates it operation for operation and
-// tests/test_multiview_emulated.py compiles the slice below, behind the slice above, on the host and holds it to that restatement bit for bit).
-// A call holds S scenes of up to V <= 32 views with PINHOLE intrinsics K_v and world -> camera poses x_v = R_v X + t_v; view 0 is the reference
-// view and a track is a row k of its key-point table: tracks[s, k, v] = the row of view v's table that track k sees, or -1.  Per track:
+// Multi-view triangulation of key-point tracks (tests/multiview_reference.py restates it operation for operation,
+// tests/tracks_reference.py restates the anchored form on that restatement's functions, and tests/test_multiview_emulated.py and
+// tests/test_tracks_emulated.py compile the slice below, behind the slice above, on the host and hold it to them bit for bit).
+// A call holds S scenes of up to V <= 32 views with PINHOLE intrinsics K_v and world -> camera poses x_v = R_v X + t_v;
+// tracks[s, k, v] = the row of view v's key-point table that track k sees, or -1.  One per-track function, mv_track<FIRST>, in two
+// instantiations that differ in the anchor view a alone: <false> a = 0, the reference view (a track is then a row of its table: 3.16);
+// <true> a = the lowest view of the observed set, for tracks that view 0 need not see (3.18).  A track with a = 0 gets the same bits from
+// both.  Per track:
 //   * observed set O: views v < n_views[s] with a table entry in range, a finite pixel and a usable pose (entries finite, R not all zero;
-//     t = 0 is a pose here); 0 not in O or |O| < 2: status 1;
-//   * hypotheses, exhaustive: for v in O \ {0} ascending, Rrel = R_v R_0', trel = t_v - Rrel t_0 (zero: skipped), E = tg_pose_E, the point of
-//     the pair (0, v) by tg_correct / tg_depths / tg_depth_status with max_depth, moved to the world frame X = R_0' (X_c0 - t_0), scored by
+//     t = 0 is a pose here); |O| < 2 or a not in O (which only <false> can meet): status 1;
+//   * hypotheses, exhaustive: for v in O, v > a ascending, Rrel = R_v R_a', trel = t_v - Rrel t_a (zero: skipped), E = tg_pose_E (mv_pair:
+//     <false> reads the three from view v's staged block, <true> calls it per hypothesis on the two staged poses), the point of
+//     the pair (a, v) by tg_correct / tg_depths / tg_depth_status with max_depth, moved to the world frame X = R_a' (X_ca - t_a), scored by
 //     MSAC sum_{w in O} min(e_w^2, thr^2) (e_w^2 the squared pixel reprojection error of X in w; thr^2 where the depth in w is not > 0 or e_w^2
 //     is not finite); the lowest score wins, ties to the lowest v; no valid hypothesis: the failure code (2, 3, 4) of the lowest-v hypothesis
 //     tried (the error is then that pair's correction, as tg_point's), none tried: 2;
-//   * inliers I: w in O with depth > 0 and e_w^2 <= thr^2 under the winner, a 32-bit mask; 0 not in I or |I| < min_views: status 5;
+//   * inliers I: w in O with depth > 0 and e_w^2 <= thr^2 under the winner, a 32-bit mask; a not in I or |I| < min_views: status 5;
 //   * refit: mv::GN_ITERS Gauss-Newton steps on sum_{w in I} e_w^2(X), I fixed, the 3x3 normal equations summed in ascending w and solved by
 //     cofactors; a step is kept only if it lowers the cost, otherwise the iteration stops;
 //   * final gates on the refined X over I, the first failing one wins: 2 not finite; 3 depth <= 0 in an inlier view; 4 depth > max_depth in one;
-//     5 max e_w^2 > thr^2; 6 min_{w in I \ {0}} cos(X - c_0, X - c_w) > cos_min (c_w = -R_w' t_w);
+//     5 max e_w^2 > thr^2; 6 min_{w in I \ {a}} cos(X - c_a, X - c_w) > cos_min (c_w = -R_w' t_w);
 //   * outputs: X as 3 fp32 (NaN unless the status is 0), the status, |I|, I, sqrt(max_{w in I} e_w^2) as fp32 (NaN for status 1 and 2).
 // Only + - * / sqrt, every product and sum rounded once, every sum over views in ascending view order.
 //
 // Launches (no workspace):
-//   track_scatter_kernel     : thread = match i of the pair (view 0, view v), grid = (chunks of 256 of max(cap, K), V - 1, S): an integer
-//                              atomicMax onto the table pre-filled with -1 (duplicate reference rows resolve to the largest candidate row:
-//                              reproducible); the threads of v = 1 also write column 0
-//   triangulate_views_kernel : thread = track, grid = (chunks of 256 of K, S); the first V threads of a workgroup put the per-view block
-//                              (mv::STRIDE doubles: R, t, calibration, centre, pose flag, Rrel, trel, E; 10.3 KB at V = 32) into LDS once;
-//                              every lane reads the same LDS address in the view loops (broadcasts); the observations are re-read from
-//                              global memory through the track table inside the loops; status counts as triangulate_kernel's
+//   track_scatter_kernel            : thread = match i of the pair (view 0, view v), grid = (chunks of 256 of max(cap, K), V - 1, S): an integer
+//                                     atomicMax onto the table pre-filled with -1 (duplicate reference rows resolve to the largest candidate
+//                                     row: reproducible); the threads of v = 1 also write column 0
+//   triangulate_views_kernel<FIRST> : thread = track, grid = (chunks of 256 of K, S); the first V threads of a workgroup put the per-view block
+//                                     (mv::STRIDE doubles: R, t, calibration, centre, pose flag by mv_stage_pose and, for <false>, Rrel, trel,
+//                                     E of the pair (0, v) by mv_stage_view; <true> leaves those three unwritten and unread; 10.3 KB at
+//                                     V = 32) into LDS once; every lane reads the same LDS address in the view loops (broadcasts); the
+//                                     observations are re-read from global memory through the track table inside the loops; status counts
+//                                     as triangulate_kernel's
 
-// ---- views solver begin (host-compilable: tests/test_multiview_emulated.py slices it out behind the solver slice above) ----
+// ---- views solver begin (host-compilable: tests/test_multiview_emulated.py and tests/test_tracks_emulated.py slice it out behind the solver
+// slice above) ----
 namespace mv {
 constexpr int MAX_VIEWS = 32;
 constexpr int GN_ITERS = 5;                 // the refit's steps (the cost stops moving after 3 at 0.5 - 2 px of noise)
@@ -481,8 +489,9 @@ constexpr int UNOBSERVED = 1;               // the other status codes are tg::'s
 constexpr int ROT = 0, TRA = 9, CAL = 12, CEN = 16, OK = 19, RREL = 20, TREL = 29, ESS = 32, STRIDE = 41;
 }  // namespace mv
 
-// the per-view block of view v: Rv (9), tv (3) its pose, Kv (9, row-major) its intrinsics, R0, t0 the pose of view 0
-__device__ inline void mv_stage_view(const double* Rv, const double* tv, const double* Kv, const double* R0, const double* t0, double* o) {
+// the first ba::STRIDE = 20 doubles of the per-view block of view v (ROT, TRA, CAL, CEN, OK): Rv (9), tv (3) its pose, Kv (9, row-major) its
+// intrinsics
+__device__ inline void mv_stage_pose(const double* Rv, const double* tv, const double* Kv, double* o) {
     bool fin = true, rnz = false;
 #pragma unroll
     for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
@@ -492,14 +501,22 @@ __device__ inline void mv_stage_view(const double* Rv, const double* tv, const d
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[mv::CEN + i] = -((Rv[i] * tv[0] + Rv[3 + i] * tv[1]) + Rv[6 + i] * tv[2]);
     o[mv::OK] = fin && rnz ? 1.0 : 0.0;
-    double Rrel[9], trel[3], E[9];
+}
+// the pair (a, v): Rrel = Rv Ra', trel = tv - Rrel ta, E = [trel]x Rrel
+__device__ inline void mv_pair(const double* Ra, const double* ta, const double* Rv, const double* tv, double* Rrel, double* trel, double* E) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = (Rv[3 * i] * R0[3 * j] + Rv[3 * i + 1] * R0[3 * j + 1]) + Rv[3 * i + 2] * R0[3 * j + 2];
+        for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = (Rv[3 * i] * Ra[3 * j] + Rv[3 * i + 1] * Ra[3 * j + 1]) + Rv[3 * i + 2] * Ra[3 * j + 2];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) trel[i] = tv[i] - ((Rrel[3 * i] * t0[0] + Rrel[3 * i + 1] * t0[1]) + Rrel[3 * i + 2] * t0[2]);
+    for (int i = 0; i < 3; ++i) trel[i] = tv[i] - ((Rrel[3 * i] * ta[0] + Rrel[3 * i + 1] * ta[1]) + Rrel[3 * i + 2] * ta[2]);
     tg_pose_E(Rrel, trel, E);
+}
+// the whole per-view block of view v for the reference instantiation: mv_stage_pose and the pair (0, v); R0, t0 the pose of view 0
+__device__ inline void mv_stage_view(const double* Rv, const double* tv, const double* Kv, const double* R0, const double* t0, double* o) {
+    mv_stage_pose(Rv, tv, Kv, o);
+    double Rrel[9], trel[3], E[9];
+    mv_pair(R0, t0, Rv, tv, Rrel, trel, E);
 #pragma unroll
     for (int k = 0; k < 9; ++k) { o[mv::RREL + k] = Rrel[k]; o[mv::ESS + k] = E[k]; }
 #pragma unroll
@@ -558,275 +575,25 @@ struct MvResult {
     double cost0, cost1;       // the refit's cost before and after (0 without a refit)
 };
 // the per-track function: vd the per-view blocks, nv = n_views[s], obs(w, u, v) = the pixel of view w through the track table (false: no
-// entry in range; u, v then NaN)
-template <class Obs>
+// entry in range; u, v then NaN).  The anchor a is view 0, which has to be observed (the reference instantiation: Rrel, trel, E of the
+// pair (0, v) are read from view v's block, mv_stage_view), or with FIRST the lowest observed view (the pair (a, v) by mv_pair per
+// hypothesis from the two blocks, which need mv_stage_pose alone).  MvResult::winner is the view of the winning hypothesis.
+template <bool FIRST, class Obs>
 __device__ inline MvResult mv_track(const double* vd, int nv, const Obs& obs, double thr2, double cos_min, double max_depth, int min_views) {
     const float nanv = __builtin_nanf("");
     MvResult o;
     o.X[0] = nanv; o.X[1] = nanv; o.X[2] = nanv; o.err = nanv;
     o.status = mv::UNOBSERVED; o.n_inliers = 0; o.inliers = 0u; o.winner = -1; o.score = 0.0; o.cost0 = 0.0; o.cost1 = 0.0;
-    // ---- the observed set
+    // ---- the observed set and the anchor
     unsigned O = 0u;
-    int nobs = 0;
+    int nobs = 0, low = -1;
     for (int w = 0; w < nv; ++w) {
         double u, v;
         const bool in = obs(w, u, v);
-        if (in && tv::is_finite(u) && tv::is_finite(v) && vd[w * mv::STRIDE + mv::OK] != 0.0) { O |= 1u << w; ++nobs; }
+        if (in && tv::is_finite(u) && tv::is_finite(v) && vd[w * mv::STRIDE + mv::OK] != 0.0) { O |= 1u << w; ++nobs; low = low < 0 ? w : low; }
     }
-    if (!(O & 1u) || nobs < 2) return o;
-    // ---- the hypotheses of the pairs (0, v)
-    double u0, v0;
-    obs(0, u0, v0);
-    double R0[9], t0[3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R0[k] = vd[mv::ROT + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t0[k] = vd[mv::TRA + k];
-    int first = -1;
-    double first_e2 = 0.0, best = 0.0, X[3] = {0.0, 0.0, 0.0};
-    for (int v = 1; v < nv; ++v) {
-        if (!((O >> v) & 1u)) continue;
-        const double* p = vd + v * mv::STRIDE;
-        double Rrel[9], trel[3], E[9], cal[8];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) trel[k] = p[mv::TREL + k];
-        if (trel[0] == 0.0 && trel[1] == 0.0 && trel[2] == 0.0) continue;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { Rrel[k] = p[mv::RREL + k]; E[k] = p[mv::ESS + k]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { cal[k] = vd[mv::CAL + k]; cal[4 + k] = p[mv::CAL + k]; }
-        double uv, vv;
-        obs(v, uv, vv);
-        const TgRays q = tg_correct(E, cal, u0, v0, uv, vv);
-        double l0, l1, zz, r[3], Xc[3];
-        tg_depths(Rrel, trel, q, l0, l1, zz, r);
-        const int st = tg_depth_status(true, q, l0, l1, zz, max_depth, Xc);
-        if (first < 0) { first = st; first_e2 = q.e2; }
-        if (st != tg::VALID) continue;
-        const double d[3] = {Xc[0] - t0[0], Xc[1] - t0[1], Xc[2] - t0[2]};
-        double Xw[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) Xw[i] = (R0[i] * d[0] + R0[3 + i] * d[1]) + R0[6 + i] * d[2];
-        double sc = 0.0;
-        for (int w = 0; w < nv; ++w) {
-            if (!((O >> w) & 1u)) continue;
-            double u, vpx, z;
-            obs(w, u, vpx);
-            const double e2 = mv_reproj(vd + w * mv::STRIDE, Xw, u, vpx, z);
-            sc = sc + (z > 0.0 && tv::is_finite(e2) && e2 < thr2 ? e2 : thr2);
-        }
-        if (o.winner < 0 || sc < best) { o.winner = v; best = sc; X[0] = Xw[0]; X[1] = Xw[1]; X[2] = Xw[2]; }
-    }
-    if (o.winner < 0) {
-        o.status = first < 0 ? tg::NOT_FINITE : first;
-        if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(first_e2);
-        return o;
-    }
-    o.score = best;
-    // ---- the inliers of the winner
-    unsigned I = 0u;
-    int ni = 0;
-    double emax = 0.0;
-    for (int w = 0; w < nv; ++w) {
-        if (!((O >> w) & 1u)) continue;
-        double u, vpx, z;
-        obs(w, u, vpx);
-        const double e2 = mv_reproj(vd + w * mv::STRIDE, X, u, vpx, z);
-        if (z > 0.0 && e2 <= thr2) { I |= 1u << w; ++ni; emax = e2 > emax ? e2 : emax; }
-    }
-    o.inliers = I; o.n_inliers = ni;
-    if (!(I & 1u) || ni < min_views) { o.status = tg::REPROJ; o.err = (float)sqrt(emax); return o; }
-    // ---- the refit on the fixed inlier set
-    double A[6], g[3];
-    double cost = mv_normal(vd, nv, obs, I, X, A, g);
-    o.cost0 = cost;
-    for (int it = 0; it < mv::GN_ITERS; ++it) {
-        double d[3], An[6], gn[3];
-        mv_step(A, g, d);
-        const double Xn[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
-        const double cn = mv_normal(vd, nv, obs, I, Xn, An, gn);
-        if (!(cn < cost)) break;
-        cost = cn; X[0] = Xn[0]; X[1] = Xn[1]; X[2] = Xn[2];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) A[k] = An[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g[k] = gn[k];
-    }
-    o.cost1 = cost;
-    // ---- the final gates
-    bool fin = tv::is_finite(X[0]) && tv::is_finite(X[1]) && tv::is_finite(X[2]), behind = false, far = false;
-    double cmin = 2.0;
-    emax = 0.0;
-    const double a[3] = {X[0] - vd[mv::CEN], X[1] - vd[mv::CEN + 1], X[2] - vd[mv::CEN + 2]};
-    const double aa = tv::dot3(a, a);
-    for (int w = 0; w < nv; ++w) {
-        if (!((I >> w) & 1u)) continue;
-        const double* p = vd + w * mv::STRIDE;
-        double u, vpx, z;
-        obs(w, u, vpx);
-        const double e2 = mv_reproj(p, X, u, vpx, z);
-        fin = fin && tv::is_finite(e2) && tv::is_finite(z);
-        behind = behind || !(z > 0.0);
-        far = far || z > max_depth;
-        emax = e2 > emax ? e2 : emax;
-        if (w > 0) {
-            const double b[3] = {X[0] - p[mv::CEN], X[1] - p[mv::CEN + 1], X[2] - p[mv::CEN + 2]};
-            const double c = tv::dot3(a, b) / sqrt(aa * tv::dot3(b, b));
-            cmin = c < cmin ? c : cmin;
-        }
-    }
-    o.status = !fin ? tg::NOT_FINITE : (behind ? tg::BEHIND : (far ? tg::FAR : (emax > thr2 ? tg::REPROJ : (cmin > cos_min ? tg::PARALLAX : tg::VALID))));
-    if (o.status != tg::NOT_FINITE) o.err = (float)sqrt(emax);
-    if (o.status == tg::VALID) { o.X[0] = (float)X[0]; o.X[1] = (float)X[1]; o.X[2] = (float)X[2]; }
-    return o;
-}
-// ---- views solver end ----
-
-struct MvArgs {
-    const float* kpts;        // (S, V, kcap, 2)
-    const int32_t* tracks;    // (S, K, V)
-    const int32_t* n_views;   // (S,) or NULL: V
-    const double* Ks;         // (S, V, 3, 3)
-    const double* Rs;         // (S, V, 3, 3)
-    const double* ts;         // (S, V, 3)
-    int K, V, kcap, min_views;
-    double thr2, cos_min, max_depth;
-    float* X;                 // (S, K, 3)
-    unsigned char* status;    // (S, K)
-    unsigned char* n_inliers;
-    int32_t* inliers;
-    float* err;
-    int32_t* info;            // (S, 8)
-};
-
-// the pixel of view w of a track through its row of the table
-struct MvObs {
-    const int32_t* row;       // (V,)
-    const float* kp;          // (V, kcap, 2)
-    unsigned kcap;
-    __device__ inline bool operator()(int w, double& u, double& v) const {
-        const unsigned r = (unsigned)row[w];                 // (-1 is a huge unsigned one)
-        const bool in = r < kcap;
-        const float nanv = __builtin_nanf("");
-        float2 q = make_float2(nanv, nanv);
-        if (in) q = *reinterpret_cast<const float2*>(kp + ((size_t)w * kcap + r) * 2);
-        u = (double)q.x; v = (double)q.y;
-        return in;
-    }
-};
-
-__global__ __launch_bounds__(256) void triangulate_views_kernel(MvArgs a) {
-    __shared__ double vd[mv::MAX_VIEWS * mv::STRIDE];
-    const int s = blockIdx.y, tid = threadIdx.x;
-    const int k = blockIdx.x * 256 + tid;
-    int nv = a.n_views ? a.n_views[s] : a.V;
-    nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
-    if (tid < a.V) {
-        const size_t v = (size_t)s * a.V + tid, v0 = (size_t)s * a.V;
-        mv_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, a.Rs + v0 * 9, a.ts + v0 * 3, vd + tid * mv::STRIDE);
-    }
-    __syncthreads();
-    const bool counted = k < a.K;
-    int st = -1;
-    if (counted) {
-        const size_t o = (size_t)s * a.K + k;
-        MvObs obs;
-        obs.row = a.tracks + o * a.V; obs.kp = a.kpts + (size_t)s * a.V * a.kcap * 2; obs.kcap = (unsigned)a.kcap;
-        const MvResult r = mv_track(vd, nv, obs, a.thr2, a.cos_min, a.max_depth, a.min_views);
-        st = r.status;
-        a.X[3 * o] = r.X[0]; a.X[3 * o + 1] = r.X[1]; a.X[3 * o + 2] = r.X[2];
-        a.status[o] = (unsigned char)st;
-        a.n_inliers[o] = (unsigned char)r.n_inliers;
-        a.inliers[o] = (int32_t)r.inliers;
-        a.err[o] = r.err;
-    }
-    // ---- status counts: one ballot per status, one atomic per wave and status
-    int32_t* info = a.info + (size_t)s * 8;
-    const bool lead = (tid & 63) == 0;
-#pragma unroll
-    for (int c = 0; c < tg::NSTATUS; ++c) {
-        const unsigned long long m = __ballot(counted && st == c);
-        if (lead && m) atomicAdd(info + 1 + c, (int)__popcll(m));
-    }
-    if (blockIdx.x == 0 && tid == 0) info[0] = a.K;        // (the counts were zeroed before the launch; nobody adds to word 0)
-}
-
-// tracks (S, K, V) pre-filled with -1: column 0 = k, column v >= 1 = the largest row of view v that the list of the pair (0, v) gives row k
-__global__ __launch_bounds__(256) void track_scatter_kernel(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int V, int cap, int K,
-                                                            int kcap, int32_t* tracks) {
-    const int s = blockIdx.z, v = blockIdx.y + 1;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    int32_t* tab = tracks + (size_t)s * K * V;
-    if (v == 1 && i < K) tab[(size_t)i * V] = i;
-    const size_t pair = (size_t)s * (V - 1) + (v - 1);
-    int n = cap > 0 ? n_matches[pair] : 0;
-    n = n > cap ? cap : n;
-    if (i >= n) return;
-    const unsigned long long r0 = (unsigned long long)idx_ref[pair * cap + i], r1 = (unsigned long long)idx_view[pair * cap + i];
-    if (r0 < (unsigned long long)K && r1 < (unsigned long long)kcap) atomicMax(tab + (size_t)r0 * V + v, (int)r1);
-}
-
-int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K, int kcap, int32_t* tracks,
-                        hipStream_t st) {
-    if (S < 1 || S > 65535 || V < 2 || V > mv::MAX_VIEWS || cap < 0 || K < 1 || kcap < 1) return -1;
-    if (hipMemsetAsync(tracks, 0xFF, (size_t)S * K * V * sizeof(int32_t), st) != hipSuccess) return -1;       // all ones: -1
-    track_scatter_kernel<<<dim3(ceil_div(cap > K ? cap : K, 256), V - 1, S), 256, 0, st>>>(idx_ref, idx_view, n_matches, V, cap, K, kcap, tracks);
-    return 0;
-}
-
-int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
-                             const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
-                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st) {
-    if (S < 1 || S > 65535 || K < 1 || V < 2 || V > mv::MAX_VIEWS || kcap < 1) return -1;
-    MvArgs a = {};
-    a.kpts = kpts; a.tracks = tracks; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts; a.K = K; a.V = V; a.kcap = kcap; a.min_views = min_views;
-    a.thr2 = max_reproj_error * max_reproj_error; a.cos_min = cos_min; a.max_depth = max_depth;
-    a.X = X; a.status = status; a.n_inliers = n_inliers; a.inliers = inliers; a.err = err; a.info = info;
-    if (hipMemsetAsync(info, 0, (size_t)S * 8 * sizeof(int32_t), st) != hipSuccess) return -1;
-    triangulate_views_kernel<<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
-    return 0;
-}
-
-// ================================================================================================================================================
-// Anchored triangulation of tracks that view 0 need not see (tests/tracks_reference.py restates it on multiview_reference's
-// functions and tests/test_tracks_emulated.py compiles the slice below, behind the two slices above, on the host).  mv_track_anchor is
-// mv_track with two changes: "view 0" is a = the lowest view of the observed set O, and status 1 is |O| < 2 alone.  Hypotheses of the pairs
-// (a, v), v in O, v > a ascending; MSAC over O; the inliers; a in I required (else status 5); the refit by mv_normal / mv_step; the gates
-// with the parallax against c_a.  Rrel, trel and E of the pair (a, v) are computed per hypothesis from the two staged view blocks in
-// mv_stage_view's operation order, so a track with a = 0 gets the bits of mv_track.  The per-view block keeps mv::STRIDE (mv_normal and
-// mv_reproj index with it); its RREL / TREL / ESS fields are not written and not read.
-//
-// Launch (no workspace): triangulate_tracks_kernel, thread = track, grid = (chunks of 256 of K, S), as triangulate_views_kernel.
-
-// ---- anchored solver begin (host-compilable: tests/test_tracks_emulated.py slices it out behind the two slices above) ----
-// the per-view block of view v without the fields of a fixed reference view: ROT, TRA, CAL, CEN, OK as mv_stage_view writes them
-__device__ inline void mva_stage_view(const double* Rv, const double* tv, const double* Kv, double* o) {
-    bool fin = true, rnz = false;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { o[mv::TRA + k] = tv[k]; fin = fin && tv::is_finite(tv[k]); }
-    o[mv::CAL] = Kv[0]; o[mv::CAL + 1] = Kv[4]; o[mv::CAL + 2] = Kv[2]; o[mv::CAL + 3] = Kv[5];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[mv::CEN + i] = -((Rv[i] * tv[0] + Rv[3 + i] * tv[1]) + Rv[6 + i] * tv[2]);
-    o[mv::OK] = fin && rnz ? 1.0 : 0.0;
-}
-// the per-track function; MvResult::winner is the view of the winning hypothesis
-template <class Obs>
-__device__ inline MvResult mv_track_anchor(const double* vd, int nv, const Obs& obs, double thr2, double cos_min, double max_depth, int min_views) {
-    const float nanv = __builtin_nanf("");
-    MvResult o;
-    o.X[0] = nanv; o.X[1] = nanv; o.X[2] = nanv; o.err = nanv;
-    o.status = mv::UNOBSERVED; o.n_inliers = 0; o.inliers = 0u; o.winner = -1; o.score = 0.0; o.cost0 = 0.0; o.cost1 = 0.0;
-    // ---- the observed set and its lowest view
-    unsigned O = 0u;
-    int nobs = 0, an = -1;
-    for (int w = 0; w < nv; ++w) {
-        double u, v;
-        const bool in = obs(w, u, v);
-        if (in && tv::is_finite(u) && tv::is_finite(v) && vd[w * mv::STRIDE + mv::OK] != 0.0) { O |= 1u << w; ++nobs; an = an < 0 ? w : an; }
-    }
-    if (nobs < 2) return o;
+    const int an = FIRST ? low : 0;
+    if (nobs < 2 || (!FIRST && !(O & 1u))) return o;        // (the lowest view of O is in O: only view 0 can be a missing anchor)
     // ---- the hypotheses of the pairs (a, v)
     const double* pa = vd + an * mv::STRIDE;
     double ua, va;
@@ -842,14 +609,19 @@ __device__ inline MvResult mv_track_anchor(const double* vd, int nv, const Obs& 
         if (!((O >> v) & 1u)) continue;
         const double* p = vd + v * mv::STRIDE;
         double Rrel[9], trel[3], E[9], cal[8];
+        // the pair (a, v): computed here or staged (the staged Rrel and E are read behind the skip: in front of it hipcc gives each of the
+        // loop's LDS reads an address register of its own)
+        if (FIRST) {
+            mv_pair(Ra, ta, p + mv::ROT, p + mv::TRA, Rrel, trel, E);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = (p[3 * i] * Ra[3 * j] + p[3 * i + 1] * Ra[3 * j + 1]) + p[3 * i + 2] * Ra[3 * j + 2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) trel[i] = p[mv::TRA + i] - ((Rrel[3 * i] * ta[0] + Rrel[3 * i + 1] * ta[1]) + Rrel[3 * i + 2] * ta[2]);
+            for (int k = 0; k < 3; ++k) trel[k] = p[mv::TREL + k];
+        }
         if (trel[0] == 0.0 && trel[1] == 0.0 && trel[2] == 0.0) continue;
-        tg_pose_E(Rrel, trel, E);
+        if (!FIRST) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { Rrel[k] = p[mv::RREL + k]; E[k] = p[mv::ESS + k]; }
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) { cal[k] = pa[mv::CAL + k]; cal[4 + k] = p[mv::CAL + k]; }
         double uv, vv;
@@ -937,17 +709,52 @@ __device__ inline MvResult mv_track_anchor(const double* vd, int nv, const Obs& 
     if (o.status == tg::VALID) { o.X[0] = (float)X[0]; o.X[1] = (float)X[1]; o.X[2] = (float)X[2]; }
     return o;
 }
-// ---- anchored solver end ----
+// ---- views solver end ----
 
-__global__ __launch_bounds__(256) void triangulate_tracks_kernel(MvArgs a) {
+struct MvArgs {
+    const float* kpts;        // (S, V, kcap, 2)
+    const int32_t* tracks;    // (S, K, V)
+    const int32_t* n_views;   // (S,) or NULL: V
+    const double* Ks;         // (S, V, 3, 3)
+    const double* Rs;         // (S, V, 3, 3)
+    const double* ts;         // (S, V, 3)
+    int K, V, kcap, min_views;
+    double thr2, cos_min, max_depth;
+    float* X;                 // (S, K, 3)
+    unsigned char* status;    // (S, K)
+    unsigned char* n_inliers;
+    int32_t* inliers;
+    float* err;
+    int32_t* info;            // (S, 8)
+};
+
+// the pixel of view w of a track through its row of the table
+struct MvObs {
+    const int32_t* row;       // (V,)
+    const float* kp;          // (V, kcap, 2)
+    unsigned kcap;
+    __device__ inline bool operator()(int w, double& u, double& v) const {
+        const unsigned r = (unsigned)row[w];                 // (-1 is a huge unsigned one)
+        const bool in = r < kcap;
+        const float nanv = __builtin_nanf("");
+        float2 q = make_float2(nanv, nanv);
+        if (in) q = *reinterpret_cast<const float2*>(kp + ((size_t)w * kcap + r) * 2);
+        u = (double)q.x; v = (double)q.y;
+        return in;
+    }
+};
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void triangulate_views_kernel(MvArgs a) {
     __shared__ double vd[mv::MAX_VIEWS * mv::STRIDE];
     const int s = blockIdx.y, tid = threadIdx.x;
     const int k = blockIdx.x * 256 + tid;
     int nv = a.n_views ? a.n_views[s] : a.V;
     nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
     if (tid < a.V) {
-        const size_t v = (size_t)s * a.V + tid;
-        mva_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * mv::STRIDE);
+        const size_t v = (size_t)s * a.V + tid, v0 = (size_t)s * a.V;
+        if (FIRST) mv_stage_pose(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * mv::STRIDE);
+        else mv_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, a.Rs + v0 * 9, a.ts + v0 * 3, vd + tid * mv::STRIDE);
     }
     __syncthreads();
     const bool counted = k < a.K;
@@ -956,7 +763,7 @@ __global__ __launch_bounds__(256) void triangulate_tracks_kernel(MvArgs a) {
         const size_t o = (size_t)s * a.K + k;
         MvObs obs;
         obs.row = a.tracks + o * a.V; obs.kp = a.kpts + (size_t)s * a.V * a.kcap * 2; obs.kcap = (unsigned)a.kcap;
-        const MvResult r = mv_track_anchor(vd, nv, obs, a.thr2, a.cos_min, a.max_depth, a.min_views);
+        const MvResult r = mv_track<FIRST>(vd, nv, obs, a.thr2, a.cos_min, a.max_depth, a.min_views);
         st = r.status;
         a.X[3 * o] = r.X[0]; a.X[3 * o + 1] = r.X[1]; a.X[3 * o + 2] = r.X[2];
         a.status[o] = (unsigned char)st;
@@ -975,16 +782,41 @@ __global__ __launch_bounds__(256) void triangulate_tracks_kernel(MvArgs a) {
     if (blockIdx.x == 0 && tid == 0) info[0] = a.K;        // (the counts were zeroed before the launch; nobody adds to word 0)
 }
 
-int launch_triangulate_tracks(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
-                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
-                              unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st) {
+// tracks (S, K, V) pre-filled with -1: column 0 = k, column v >= 1 = the largest row of view v that the list of the pair (0, v) gives row k
+__global__ __launch_bounds__(256) void track_scatter_kernel(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int V, int cap, int K,
+                                                            int kcap, int32_t* tracks) {
+    const int s = blockIdx.z, v = blockIdx.y + 1;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int32_t* tab = tracks + (size_t)s * K * V;
+    if (v == 1 && i < K) tab[(size_t)i * V] = i;
+    const size_t pair = (size_t)s * (V - 1) + (v - 1);
+    int n = cap > 0 ? n_matches[pair] : 0;
+    n = n > cap ? cap : n;
+    if (i >= n) return;
+    const unsigned long long r0 = (unsigned long long)idx_ref[pair * cap + i], r1 = (unsigned long long)idx_view[pair * cap + i];
+    if (r0 < (unsigned long long)K && r1 < (unsigned long long)kcap) atomicMax(tab + (size_t)r0 * V + v, (int)r1);
+}
+
+int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K, int kcap, int32_t* tracks,
+                        hipStream_t st) {
+    if (S < 1 || S > 65535 || V < 2 || V > mv::MAX_VIEWS || cap < 0 || K < 1 || kcap < 1) return -1;
+    if (hipMemsetAsync(tracks, 0xFF, (size_t)S * K * V * sizeof(int32_t), st) != hipSuccess) return -1;       // all ones: -1
+    track_scatter_kernel<<<dim3(ceil_div(cap > K ? cap : K, 256), V - 1, S), 256, 0, st>>>(idx_ref, idx_view, n_matches, V, cap, K, kcap, tracks);
+    return 0;
+}
+
+int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
+                             const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
+                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, bool first,
+                             hipStream_t st) {
     if (S < 1 || S > 65535 || K < 1 || V < 2 || V > mv::MAX_VIEWS || kcap < 1) return -1;
     MvArgs a = {};
     a.kpts = kpts; a.tracks = tracks; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts; a.K = K; a.V = V; a.kcap = kcap; a.min_views = min_views;
     a.thr2 = max_reproj_error * max_reproj_error; a.cos_min = cos_min; a.max_depth = max_depth;
     a.X = X; a.status = status; a.n_inliers = n_inliers; a.inliers = inliers; a.err = err; a.info = info;
     if (hipMemsetAsync(info, 0, (size_t)S * 8 * sizeof(int32_t), st) != hipSuccess) return -1;
-    triangulate_tracks_kernel<<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
+    if (first) triangulate_views_kernel<true><<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
+    else triangulate_views_kernel<false><<<dim3(ceil_div(K, 256), S), 256, 0, st>>>(a);
     return 0;
 }
 
@@ -1020,21 +852,12 @@ int launch_triangulate_tracks(const float* kpts, int kcap, const int32_t* tracks
 // ---- bundle solver begin (host-compilable: tests/test_bundle_emulated.py slices it out behind the two slices above) ----
 namespace ba {
 constexpr int MIN_VIEW_OBS = 6;             // fewer observations than the 6 parameters of a pose: the view is held
-constexpr int STRIDE = 20;                  // the per-view block: mv::ROT, mv::TRA, mv::CAL, mv::OK of mv's block (what mv_reproj reads)
+constexpr int STRIDE = 20;                  // the per-view block: what mv_stage_pose writes (mv_reproj reads mv::ROT, mv::TRA, mv::CAL of it)
 constexpr double FTOL = 1e-8;               // noise-free scenes stop moving by more than 9.3e-9 relative once they are down to rounding
 constexpr double LAMBDA0 = 1e-3, LAMBDA_MIN = 1e-10, LAMBDA_MAX = 1e10;
 constexpr int ST_OK = 0, ST_NOTHING = 1, ST_NOT_FINITE = 2;
 }  // namespace ba
 
-__device__ inline void ba_stage_view(const double* Rv, const double* tv, const double* Kv, double* o) {
-    bool fin = true, rnz = false;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { o[mv::ROT + k] = Rv[k]; fin = fin && tv::is_finite(Rv[k]); rnz = rnz || Rv[k] != 0.0; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { o[mv::TRA + k] = tv[k]; fin = fin && tv::is_finite(tv[k]); o[mv::CEN + k] = 0.0; }
-    o[mv::CAL] = Kv[0]; o[mv::CAL + 1] = Kv[4]; o[mv::CAL + 2] = Kv[2]; o[mv::CAL + 3] = Kv[5];
-    o[mv::OK] = fin && rnz ? 1.0 : 0.0;
-}
 // Huber's rho of e^2 at c pixels (c = +inf: e^2) and the weight of the observation
 __device__ inline double ba_rho(double e2, double c, double& wt) {
     const double e = sqrt(e2);
@@ -1322,7 +1145,7 @@ __device__ inline void ba_stage_state(const BaArgs& a, int s, int which, double*
     const int tid = threadIdx.x;
     if (tid < a.V) {
         const double* p = a.pose + (((size_t)s * 2 + which) * a.V + tid) * 12;
-        ba_stage_view(p, p + 9, a.Ks + ((size_t)s * a.V + tid) * 9, vd + tid * ba::STRIDE);
+        mv_stage_pose(p, p + 9, a.Ks + ((size_t)s * a.V + tid) * 9, vd + tid * ba::STRIDE);
     }
 }
 
@@ -1334,7 +1157,7 @@ __global__ __launch_bounds__(256) void ba_init_kernel(BaArgs a) {
     const int nv = ba_nv(a, s);
     if (tid < a.V) {
         const size_t v = (size_t)s * a.V + tid;
-        ba_stage_view(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * ba::STRIDE);
+        mv_stage_pose(a.Rs + v * 9, a.ts + v * 3, a.Ks + v * 9, vd + tid * ba::STRIDE);
     }
     __syncthreads();
     unsigned M = 0u;
@@ -1487,7 +1310,7 @@ __global__ __launch_bounds__(256) void ba_schur_kernel(BaArgs a) {
     if (tid < 2) {
         const int x = tid == 0 ? v : w;
         const double* p = a.pose + (((size_t)s * 2 + c.cur) * a.V + x) * 12;
-        ba_stage_view(p, p + 9, a.Ks + ((size_t)s * a.V + x) * 9, pvw + tid * ba::STRIDE);
+        mv_stage_pose(p, p + 9, a.Ks + ((size_t)s * a.V + x) * 9, pvw + tid * ba::STRIDE);
     }
     __syncthreads();
     if (v == w) ba_schur_block<true>(a, s, v, w, c, pvw, red, out, rhs);

@@ -133,13 +133,11 @@ int launch_recover_pose(const float* p0, const float* p1, const int64_t* idx0, c
 // (multi-view triangulation of key-point tracks: the track table of a reference view, the point of each track from all the views that see it)
 int launch_build_tracks(const int64_t* idx_ref, const int64_t* idx_view, const int32_t* n_matches, int S, int V, int cap, int K, int kcap, int32_t* tracks,
                         hipStream_t st);
+// (first = false: view 0 anchors every track; true: the lowest view that observes a track anchors it, so view 0 need not see it)
 int launch_triangulate_views(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
-                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st);
-// (the same for tracks that view 0 need not see: the anchor of a track is the lowest view that observes it)
-int launch_triangulate_tracks(const float* kpts, int kcap, const int32_t* tracks, const int32_t* n_views, int S, int K, int V, const double* Ks,
-                              const double* Rs, const double* ts, double max_reproj_error, double cos_min, double max_depth, int min_views, float* X,
-                              unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, hipStream_t st);
+                             unsigned char* status, unsigned char* n_inliers, int32_t* inliers, float* err, int32_t* info, bool first,
+                             hipStream_t st);
 // (bundle adjustment of the poses of the free views and the points of the valid tracks: Levenberg-Marquardt through the Schur complement)
 size_t bundle_workspace_bytes(int S, int K, int V);
 int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, const int32_t* inlier_views, const float* points3d, const int32_t* n_views,

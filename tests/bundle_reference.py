@@ -25,7 +25,8 @@ _ERR = dict(all="ignore")
 
 
 def stage_view(Rv, tv, Kv):
-    """ba_stage_view: the part of multiview_reference.stage_view's block that mv_reproj reads, and the pose flag."""
+    """mv_stage_pose, which stages the bundle kernels' views: the first 20 doubles of multiview_reference.stage_view's block (of them the
+    bundle solver reads what mv_reproj reads, and the pose flag; the centre is written and not read)."""
     return MR.stage_view(Rv, tv, Kv, Rv, tv)
 
 

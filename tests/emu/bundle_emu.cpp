@@ -58,7 +58,7 @@ static double chunk_sum(const std::vector<double>& per_track) {
     return tot;
 }
 static void stage(const std::vector<double>& pose, const std::vector<double>& cam, int V, std::vector<double>& vd) {
-    for (int v = 0; v < V; ++v) ba_stage_view(&pose[(size_t)v * 12], &pose[(size_t)v * 12 + 9], &cam[(size_t)v * 21 + 12], &vd[(size_t)v * ba::STRIDE]);
+    for (int v = 0; v < V; ++v) mv_stage_pose(&pose[(size_t)v * 12], &pose[(size_t)v * 12 + 9], &cam[(size_t)v * 21 + 12], &vd[(size_t)v * ba::STRIDE]);
 }
 int main() {
     int G = 0;

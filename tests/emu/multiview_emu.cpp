@@ -1,4 +1,4 @@
-// The views-solver slice of csrc/k_triangulate.hip (mv_stage_view, mv_track: the observed set, the hypotheses of the pairs (0, v), MSAC
+// The views-solver slice of csrc/k_triangulate.hip (mv_stage_view, mv_track<false>: the observed set, the hypotheses of the pairs (0, v), MSAC
 // scores, inlier views, the Gauss-Newton refit, the final gates; sliced out of the product source behind the two-view solver slice and the
 // shared geometry of csrc/twoview_math.hpp by tests/test_multiview_emulated.py into multiview_slice.hpp) on the host.
 // stdin: G int32, then per scene fp64: V, nv, m, min_views, thr2, cos_min, max_depth, V x (R (9), t (3), K (9)), m x V x (u, v, in range 0 / 1)
@@ -41,7 +41,7 @@ int main() {
             xfh::mv_stage_view(&cam[(size_t)v * 21], &cam[(size_t)v * 21 + 9], &cam[(size_t)v * 21 + 12], &cam[0], &cam[9], &vd[(size_t)v * xfh::mv::STRIDE]);
         for (int k = 0; k < m; ++k) {
             HostObs o{&obs[(size_t)k * V * 3]};
-            const xfh::MvResult r = xfh::mv_track(vd.data(), nv, o, hdr[4], hdr[5], hdr[6], min_views);
+            const xfh::MvResult r = xfh::mv_track<false>(vd.data(), nv, o, hdr[4], hdr[5], hdr[6], min_views);
             iv.insert(iv.end(), {r.status, r.n_inliers, (int32_t)r.inliers, r.winner});
             fv.insert(fv.end(), {r.X[0], r.X[1], r.X[2], r.err});
             dv.insert(dv.end(), {r.score, r.cost0, r.cost1});

@@ -1,5 +1,5 @@
 """float64 numpy restatement of the multi-view triangulation of csrc/k_triangulate.hip: the per-view block (mv_stage_view),
-the per-track function (mv_track: observed set, the exhaustive hypotheses of the pairs (0, v) by structure_reference's tg_* restatements,
+the per-track function (mv_track<false>: observed set, the exhaustive hypotheses of the pairs (0, v) by structure_reference's tg_* restatements,
 MSAC scores, inlier views, the Gauss-Newton refit, the final gates) and the track table (a maximum-scatter).
 
 It performs the kernel's operations in the kernel's order, vectorised over the tracks of one scene (numpy never fuses a multiply and an add;
@@ -39,7 +39,7 @@ def build_tracks(idx_ref, idx_view, n_matches, K, kcap=None):
 
 
 def stage_view(Rv, tv, Kv, R0, t0):
-    """mv_stage_view: the per-view block as a dict of lists of float64 scalars."""
+    """mv_stage_view (mv_stage_pose, then mv_pair): the per-view block as a dict of lists of float64 scalars."""
     Rv, R0 = [np.float64(x) for x in np.asarray(Rv, np.float64).reshape(9)], [np.float64(x) for x in np.asarray(R0, np.float64).reshape(9)]
     tv, t0 = [np.float64(x) for x in np.asarray(tv, np.float64).reshape(3)], [np.float64(x) for x in np.asarray(t0, np.float64).reshape(3)]
     Kv = np.asarray(Kv, np.float64).reshape(9)

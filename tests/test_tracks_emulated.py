@@ -4,9 +4,10 @@ The track-graph slice of csrc/k_tracks.hip (tests/emu/tracks_emu.cpp) runs with 
 forward, reversed and shuffled must give the restatement's labels, view masks, inconsistency flags, counters and tables, for V in {2, 3, 32}
 and K in {1, 64, 300}, the zigzag (the deepest parent chain two views can make) included.
 
-The anchored-solver slice of csrc/k_triangulate.hip (tests/emu/tracks_anchor_emu.cpp, fp contraction off; behind the two-view and the
-views-solver slices of the same file) must equal the restatement bit for bit on tests/multiview_support.mixed_scene's eight kinds at
-V in {2, 3, 8, 32} with view 0's column emptied on a third of the tracks, and must equal mv_track wherever the anchor is view 0."""
+The views-solver slice of csrc/k_triangulate.hip anchored at the lowest observing view, mv_track<true> (tests/emu/tracks_anchor_emu.cpp, fp
+contraction off; behind the two-view slice of the same file), must equal the restatement bit for bit on tests/multiview_support.mixed_scene's
+eight kinds at V in {2, 3, 8, 32} with view 0's column emptied on a third of the tracks, and must equal the reference instantiation
+mv_track<false> wherever the anchor is view 0."""
 import subprocess
 
 import numpy as np
@@ -20,7 +21,7 @@ import twoview_support as TS
 from test_multiview_emulated import _record          # the scene record of tests/emu/multiview_emu.cpp, which tracks_anchor_emu.cpp reads too
 
 G_BEGIN, G_END = "// ---- track graph begin", "// ---- track graph end"
-A_BEGIN, A_END = "// ---- anchored solver begin", "// ---- anchored solver end"
+V_BEGIN, V_END = "// ---- views solver begin", "// ---- views solver end"
 
 
 @pytest.fixture(scope="module")
@@ -33,25 +34,29 @@ def graph_bin():
 @pytest.fixture(scope="module")
 def anchor_bin():
     two = TS.slice_solver("k_triangulate.hip", "// ---- solver begin", "// ---- solver end")
-    _, views = TS._between("k_triangulate.hip", "// ---- views solver begin", "// ---- views solver end")
-    _, anchored = TS._between("k_triangulate.hip", A_BEGIN, A_END)
-    for s in (views, anchored):
-        assert "__shared__" not in s and "asm" not in s and "__builtin_amdgcn" not in s
-    return TS.build_emu("tracks_anchor_slice.hpp", "tracks_anchor_emu", two + (views + anchored).replace("__device__ ", ""))
+    _, views = TS._between("k_triangulate.hip", V_BEGIN, V_END)
+    assert "__shared__" not in views and "asm" not in views and "__builtin_amdgcn" not in views
+    return TS.build_emu("tracks_anchor_slice.hpp", "tracks_anchor_emu", two + views.replace("__device__ ", ""))
 
 
 def test_the_slices_are_what_the_issue_asks_of_the_device_code():
     text = open(TS.CSRC + "/k_triangulate.hip").read()
-    _, anchored = TS._between("k_triangulate.hip", A_BEGIN, A_END)
-    assert text.index("#pragma clang fp contract(off)") < text.index("// ---- views solver end") < text.index(A_BEGIN) < text.index(A_END)
+    _, views = TS._between("k_triangulate.hip", V_BEGIN, V_END)
+    assert text.index("#pragma clang fp contract(off)") < text.index("// ---- solver end") < text.index(V_BEGIN) < text.index(V_END)
+    assert "__shared__" not in views and "asm" not in views and "__builtin_amdgcn" not in views
     for word in ("sin(", "cos(", "acos(", "atan", "pow(", "exp(", "log(", "atomic"):
-        assert word not in anchored, word
-    # the functions of the two slices in front are called, not duplicated
-    for name in ("tg_correct(", "tg_depths(", "tg_depth_status(", "tg_pose_E(", "mv_reproj(", "mv_normal(", "mv_step("):
-        assert name in anchored, name
+        assert word not in views, word
+    # one per-track function for both anchors: it calls the helpers of the two-view slice and of its own slice, and nothing is written twice
+    track = views[views.index("MvResult mv_track("):]
+    for name in ("tg_correct(", "tg_depths(", "tg_depth_status(", "mv_pair(", "mv_reproj(", "mv_normal(", "mv_step("):
+        assert name in track, name
         for kind in ("inline TgRays ", "void ", "int ", "double "):
-            assert kind + name not in anchored, name
-    assert text.count("double mv_reproj(") == 1 and text.count("void mv_step(") == 1 and text.count("MvResult mv_track_anchor(") == 1
+            assert kind + name not in track, name
+    assert "tg_pose_E(" in views and "void tg_pose_E(" not in views
+    for definition in ("double mv_reproj(", "double mv_normal(", "void mv_step(", "void mv_pair(", "void mv_stage_pose(", "void mv_stage_view(",
+                       "MvResult mv_track("):
+        assert text.count(definition) == 1, definition
+    assert "mv_track_anchor" not in text and "mva_stage_view" not in text and "ba_stage_view" not in text
     graph = open(TS.CSRC + "/k_tracks.hip").read()
     _, g = TS._between("k_tracks.hip", G_BEGIN, G_END)
     for name in ("tk_union(", "tk_find(", "tk_see("):
@@ -157,13 +162,13 @@ def test_anchored_tracks_equal_the_restatement_bit_for_bit(anchor_bin):
         want = np.stack([w["score"], w["cost0"], w["cost1"]], axis=1)
         assert np.array_equal(dv[s], want.view(np.uint64)), (g, np.nonzero(dv[s] != want.view(np.uint64))[0][:5])
         assert (np.isnan(w["points3d"]).all(axis=1) == (w["status"] != 0)).all() and np.isfinite(w["points3d"][w["status"] == 0]).all()
-        # wherever the anchor is view 0: the bits of mv_track (NaN payloads included)
+        # wherever the anchor is view 0: the bits of mv_track<false> (NaN payloads included)
         zero = np.zeros(H, bool)
         zero[s] = w["anchor"] == 0
         assert np.array_equal(iv[zero], riv[zero]) and np.array_equal(dv[zero], rdv[zero]), g
         nan = np.isnan(fv[zero].view(np.float32)) & np.isnan(rfv[zero].view(np.float32))
         assert np.array_equal(fv[zero][~nan], rfv[zero][~nan]), g
-        # every other track is unobserved for mv_track
+        # every other track is unobserved for mv_track<false>
         assert (riv[s, 0][w["anchor"] != 0] == MR.UNOBSERVED).all(), g
         zero_n += int(zero.sum())
         seen += np.bincount(w["status"], minlength=7)

@@ -1,4 +1,4 @@
-"""numpy restatement of the tracks over a graph of view pairs (csrc/k_tracks.hip) and of the anchored triangulation (mv_track_anchor of
+"""numpy restatement of the tracks over a graph of view pairs (csrc/k_tracks.hip) and of the anchored triangulation (mv_track<true> of
 csrc/k_triangulate.hip), DESIGN.md 3.18.
 
 ``build_tracks_graph`` is a sequential union-find with minimum labels: the label of a component is its smallest node id v K + row, the
@@ -92,7 +92,7 @@ def build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, V, K, min_length=2, 
 
 
 def observed(kpts, tracks, n_views, Rs, ts, Ks, pixels64=False):
-    """The observed sets of mv_track / mv_track_anchor: (nv, K) bool, view w observes track k (an entry in range, a finite pixel, a usable pose)."""
+    """The observed sets of mv_track<false> / mv_track<true>: (nv, K) bool, view w observes track k (an entry in range, a finite pixel, a usable pose)."""
     kpts = np.asarray(kpts, np.float64 if pixels64 else np.float32).astype(np.float64)
     tracks = np.asarray(tracks, np.int64)
     V, kcap = kpts.shape[0], kpts.shape[1]
@@ -111,7 +111,7 @@ def observed(kpts, tracks, n_views, Rs, ts, Ks, pixels64=False):
 def triangulate_views(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=4.0, min_parallax_deg=1.0, max_depth=math.inf, min_views=2,
                       pixels64=False, anchor="first"):
     """One scene, the arguments of multiview_reference.triangulate_views.  anchor='reference' is that function; anchor='first' restates
-    mv_track_anchor.  Returns a dict: points3d (K,3) float32, status, n_inliers (K,) uint8, inlier_views (K,) int32, reproj_error (K,)
+    mv_track<true>.  Returns a dict: points3d (K,3) float32, status, n_inliers (K,) uint8, inlier_views (K,) int32, reproj_error (K,)
     float32, valid, info (8,), winner (K,) (the view of the winning hypothesis, -1: none), score, cost0, cost1 (K,) float64, anchor (K,)
     (-1: nothing observes the track) and groups: [(anchor, the track indices, multiview_reference's result for them)]."""
     gates = dict(max_reproj_error=max_reproj_error, min_parallax_deg=min_parallax_deg, max_depth=max_depth, min_views=min_views, pixels64=pixels64)
