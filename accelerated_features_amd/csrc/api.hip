@@ -1255,6 +1255,35 @@ int xfh_bundle_adjust(const float* kpts, int kpt_cap, const int32_t* tracks, con
     return check_launch(who);
 }
 
+// ---- pose-graph initialisation (k_triangulate.hip): every check returns before any launch
+size_t xfh_pose_graph_workspace_bytes(int S, int P, int V) {
+    if (S <= 0 || S > 65535 || P <= 0 || P > (1 << 20) || V < 2 || V > 32) return 0;
+    return xfh::pose_graph_workspace_bytes(S, P, V);
+}
+
+int xfh_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
+                      int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
+                      double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* workspace, size_t workspace_bytes,
+                      xfh_stream stream) {
+    const char* who = "xfh_average_poses";
+    if (!view_pairs || !R_rel || !t_rel || !weight || !Rs_out || !ts_out || !registered || !edge_factor || !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (P < 1 || P > (1 << 20)) return fail(XFH_ERR_ARG, "%s: P %d outside [1, 2^20]", who, P);
+    if (iterations < 1 || iterations > 1000) return fail(XFH_ERR_ARG, "%s: iterations %d outside [1, 1000]", who, iterations);
+    if (redescend < 0 || redescend > iterations) return fail(XFH_ERR_ARG, "%s: redescend %d outside [0, iterations]", who, redescend);
+    if (!(rot_scale_rad > 0.0) || !(rot_scale_rad < 4.0)) return fail(XFH_ERR_ARG, "%s: rot_scale_rad %g outside (0, 4)", who, rot_scale_rad);
+    if (!(pos_scale_sin > 0.0) || !(pos_scale_sin <= 1.0)) return fail(XFH_ERR_ARG, "%s: pos_scale_sin %g outside (0, 1]", who, pos_scale_sin);
+    if (!(min_pivot_ratio >= 0.0) || !(min_pivot_ratio < 1.0)) return fail(XFH_ERR_ARG, "%s: min_pivot_ratio %g outside [0, 1)", who, min_pivot_ratio);
+    int rc = check_ws(workspace, workspace_bytes, xfh::pose_graph_workspace_bytes(S, P, V));
+    if (rc) return rc;
+    if (launch_average_poses(view_pairs, R_rel, t_rel, weight, n_views, S, P, V, iterations, redescend, rot_scale_rad, pos_scale_sin, min_pivot_ratio,
+                             Rs_out, ts_out, registered, edge_factor, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

@@ -1499,4 +1499,599 @@ int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, con
     return 0;
 }
 
+// ================================================================================================================================================
+// Pose-graph initialisation: the world -> camera poses of the V <= 32 views of a scene from the relative poses of P pairs of views (DESIGN.md
+// 3.19; tests/posegraph_reference.py restates it operation for operation and tests/test_posegraph_emulated.py compiles the slice below, behind
+// the three slices above, on the host and holds it to that restatement bit for bit).  Edge p = (a, b) carries R_rel, t_rel with
+// x_b = R_rel x_a + t_rel (R_rel = R_b R_a', t_rel parallel to R_b (c_a - c_b), c_v = -R_v' t_v) and a weight.  Gauge R_0 = I, c_0 = 0.
+//   * an edge is valid when a != b, both views are in [0, n_views), the weight is finite and > 0 and R_rel is finite; a valid edge has a
+//     direction when t_rel is finite and n2 = (t0 t0 + t1 t1) + t2 t2 is finite and > 0;
+//   * spanning tree: view 0 is reached; repeat: of the valid edges with exactly one reached endpoint the largest weight, ties to the lowest
+//     pair index; the new view's rotation is R_b = R_rel R_a or R_a = R_rel' R_b (every entry (x y + x y) + x y).  Views never reached are
+//     unregistered (NaN poses, bit of `registered` clear) and the valid edges between them drop out; the edges left are the active ones.  The
+//     unknowns are the registered views but 0, ascending, numbered compactly: n_r views;
+//   * rotations, `iterations` rounds on R_v <- R_v cay(delta_v) (ba_pose_update): the residual of an active edge is r = 2 vec(q), q the
+//     quaternion of E = R_b' (R_rel R_a) by the branch on the trace and the largest diagonal entry (s = 2 sqrt(.), the component of the branch
+//     s / 4, the others a sum or difference of two entries over s), divided by its norm, its sign that of a scalar part >= 0;
+//     |r| = sqrt((r0 r0 + r1 r1) + r2 r2).  The factor of round k: Huber's (|r| > c ? c / |r| : 1) for k < iterations - redescend, Cauchy's
+//     c c / (c c + |r| |r|) for the later rounds, w_p = weight_p factor.  To first order r' = r + delta_a - delta_b: the round solves the
+//     weighted graph Laplacian (packed lower triangle over the unknowns: diagonal + w_p at both ends, entry (a, b) - w_p; right-hand sides
+//     - w_p r at a, + w_p r at b, one per coordinate) by ba_cholesky_solve, once per coordinate on a copy of the triangle; a failed
+//     factorisation leaves the rotations of the round as they are.  After the last round the residuals and factors are taken once more
+//     with the last round's loss: those are the final rotation factors;
+//   * positions, the rotations fixed: d_p = R_b' (t_rel / sqrt(n2)) is the direction of c_a - c_b.  Round k: w_p = weight_p factor over the
+//     active edges with a direction, factor 1 in round 0 and else from rho = |e - (d.e) d| / |e| (d.e > 0, else 1) of e = c_a - c_b at the
+//     positions of the round before, with c = pos_scale_sin and the losses as above.  M: 3x3 blocks + w_p (I - d d') on the diagonal of both
+//     ends and - w_p (I - d d') between them (entry (x, y): w_p ((x == y) - d_x d_y)); g: + w_p d at a, - w_p d at b; view 0 is left out:
+//     n = 3 n_r.  mu = tr(M) / (g.g), both summed in ascending index; A = M + (mu g_i) g_j; solve A c = g by ba_cholesky_solve.  The
+//     rigidity test: the smallest pivot^2 / (the entry of A's diagonal before the factorisation) must be >= min_pivot_ratio.  The scale:
+//     c <- c / s, s = sum_p w_p d_p.(c_a - c_b) / sum_p w_p.  A failed factorisation or test, mu or s not finite or not > 0: the scene's
+//     status is ROTATIONS_ONLY, the positions of every view but 0 NaN, the position factors 0.  After the last round the residuals and
+//     factors once more (the final position factors), then t_v = -(R_v c_v);
+//   * sums: every entry of a matrix or vector adds its edges in ascending pair index; every sum over edges is taken in rs::block_sums'
+//     order (pg_sum: slot i of 256 adds the edges i, i + 256, ..., 8 segments of 32 slots in order, the tree over the 8);
+//   * info: valid edges, registered views, valid edges with a direction, active edges with a final rotation factor < 0.5, position edges
+//     with a final position factor < 0.5, n = 3 n_r, status, 0.  Status: NOTHING (no valid edge at view 0: R_0 = I, t_0 = 0, the rest NaN),
+//     else NOT_FINITE (an output of a registered view is not finite), else ROTATIONS_ONLY, else OK.
+// Only + - * / sqrt, every product and sum rounded once, no floating-point atomics: two calls give the same bits.
+//
+// One launch per call: pose_graph_kernel, one workgroup of 256 per scene, runs the tree and all the rounds without leaving.  LDS: the packed
+// 93 x 93 triangle with its right-hand side, pivots and diagonal (36.3 KB; the rotation rounds keep their 31 x 31 systems in its front),
+// the rotations and centres (3 KB), the sums' and the tree's selection buffers.  Per-edge keys, weights, residuals, directions and the
+// sums' terms live in the workspace (pose_graph_workspace_bytes).
+
+// ---- pose graph begin (host-compilable: tests/test_posegraph_emulated.py slices it out behind the three slices above) ----
+namespace pg {
+constexpr int ST_OK = 0, ST_NOTHING = 1, ST_ROTATIONS_ONLY = 2, ST_NOT_FINITE = 3;
+constexpr int MAXU = mv::MAX_VIEWS - 1, NPOS = 3 * MAXU, TRI = NPOS * (NPOS + 1) / 2;
+// the scene's fp64 LDS: the position system, then the state
+constexpr int L_SYS = 0, L_RHS = TRI, L_PIV = L_RHS + NPOS, L_DIAG = L_PIV + NPOS, L_ROT = L_DIAG + NPOS, L_CEN = L_ROT + 9 * mv::MAX_VIEWS;
+constexpr int L_RED = L_CEN + 3 * mv::MAX_VIEWS, L_BW = L_RED + 264, L_SC = L_BW + 256, L_END = L_SC + 8;
+// the rotation rounds inside L_SYS: the triangle, its working copy, three right-hand sides of 32, the pivots
+constexpr int R_TRI = 0, R_WORK = 512, R_RHS = 1024, R_PIV = 1120;
+// the scene's int LDS: the tree's selection, compact index of a view (-1: none), view of a compact index, the tree's edges, words
+constexpr int I_BP = 0, I_IDX = 256, I_VIEW = 288, I_TREE = 320, I_REG = 352, I_NR = 353, I_END = 360;
+constexpr int K_DIR = 1 << 16, K_ACTIVE = 1 << 17;          // key of a valid edge: a | b << 8 | flags; -1: not valid
+constexpr int HUBER = 0, CAUCHY = 1;
+}  // namespace pg
+
+struct PgScene {
+    const int32_t* pairs;     // (P, 2)
+    const double* Rrel;       // (P, 9)
+    const double* trel;       // (P, 3)
+    const double* weight;     // (P,)
+    int nv, P, V, iterations, redescend;
+    double crot, cpos, min_ratio;
+    double* Rs;               // (V, 9)
+    double* ts;               // (V, 3)
+    int32_t* registered;      // (1,)
+    double* factor;           // (P, 2)
+    int32_t* info;            // (8,)
+    int32_t* key;             // workspace (P,)
+    double* wcur;             // (P,)
+    double* res;              // (P, 3)
+    double* dir;              // (P, 3)
+    double* ta;               // (P,)
+    double* tb;               // (P,)
+    double* lds;              // pg::L_END
+    int* ldi;                 // pg::I_END
+};
+
+// the total of x[0 .. P) in rs::block_sums' order, on every thread
+template <class Sync>
+__device__ inline double pg_sum(const double* x, int P, double* red, int tid, int nt, const Sync& sync) {
+    sync();
+    for (int i = tid; i < 256; i += nt) {
+        double t = 0.0;
+        for (int p = i; p < P; p += 256) t = t + x[p];
+        red[i] = t;
+    }
+    sync();
+    for (int j = tid; j < 8; j += nt) {
+        double t = 0.0;
+        for (int i = 0; i < 32; ++i) t = t + red[32 * j + i];
+        red[256 + j] = t;
+    }
+    sync();
+    const double* q = red + 256;
+    return (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])));
+}
+__device__ inline double pg_factor(double x, double c, int kind) {
+    if (kind == pg::CAUCHY) return (c * c) / (c * c + x * x);
+    return x > c ? c / x : 1.0;
+}
+__device__ inline int pg_kind(const PgScene& s, int k) { return k < s.iterations - s.redescend ? pg::HUBER : pg::CAUCHY; }
+// C = A B, or A' B with TA
+template <bool TA>
+__device__ inline void pg_mul(const double* A, const double* B, double* C) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            C[3 * i + j] = TA ? (A[i] * B[j] + A[3 + i] * B[3 + j]) + A[6 + i] * B[6 + j] : (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+// the keys of the edges: valid, views, direction
+template <class Sync>
+__device__ inline void pg_keys(const PgScene& s, int tid, int nt, const Sync& sync) {
+    for (int p = tid; p < s.P; p += nt) {
+        const int a = s.pairs[2 * p], b = s.pairs[2 * p + 1];
+        const double w = s.weight[p];
+        bool ok = a != b && a >= 0 && a < s.nv && b >= 0 && b < s.nv && tv::is_finite(w) && w > 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) ok = ok && tv::is_finite(s.Rrel[(size_t)9 * p + k]);
+        const double t0 = s.trel[(size_t)3 * p], t1 = s.trel[(size_t)3 * p + 1], t2 = s.trel[(size_t)3 * p + 2];
+        const double n2 = (t0 * t0 + t1 * t1) + t2 * t2;
+        const bool dir = tv::is_finite(t0) && tv::is_finite(t1) && tv::is_finite(t2) && tv::is_finite(n2) && n2 > 0.0;
+        s.key[p] = ok ? (a | (b << 8) | (dir ? pg::K_DIR : 0)) : -1;
+    }
+    sync();
+}
+// the spanning tree: rotations of the reached views in LDS, the mask, the compact numbering; marks the active edges
+template <class Sync>
+__device__ inline void pg_tree(const PgScene& s, int tid, int nt, const Sync& sync) {
+    double* rot = s.lds + pg::L_ROT;
+    double* bw = s.lds + pg::L_BW;
+    int* bp = s.ldi + pg::I_BP;
+    for (int i = tid; i < 9 * mv::MAX_VIEWS; i += nt) rot[i] = (i % 9) % 4 == 0 ? 1.0 : 0.0;
+    for (int i = tid; i < 3 * mv::MAX_VIEWS; i += nt) s.lds[pg::L_CEN + i] = 0.0;
+    for (int i = tid; i < 32; i += nt) s.ldi[pg::I_TREE + i] = -1;
+    if (tid == 0) s.ldi[pg::I_REG] = 1;
+    sync();
+    for (int step = 0; step + 1 < s.nv; ++step) {
+        const unsigned reg = (unsigned)s.ldi[pg::I_REG];
+        for (int i = tid; i < 256; i += nt) {
+            double w = -1.0;
+            int at = -1;
+            for (int p = i; p < s.P; p += 256) {
+                const int k = s.key[p];
+                if (k < 0) continue;
+                if (((reg >> (k & 255)) & 1u) == ((reg >> ((k >> 8) & 255)) & 1u)) continue;
+                const double wp = s.weight[p];
+                if (wp > w) { w = wp; at = p; }
+            }
+            bw[i] = w; bp[i] = at;
+        }
+        sync();
+        for (int h = 128; h > 0; h >>= 1) {
+            for (int i = tid; i < h; i += nt) {
+                const double w0 = bw[i], w1 = bw[i + h];
+                const int p0 = bp[i], p1 = bp[i + h];
+                const bool second = p1 >= 0 && (p0 < 0 || w1 > w0 || (w1 == w0 && p1 < p0));
+                if (second) { bw[i] = w1; bp[i] = p1; }
+            }
+            sync();
+        }
+        const int p = bp[0];
+        if (p < 0) break;
+        if (tid == 0) {
+            const int k = s.key[p], a = k & 255, b = (k >> 8) & 255;
+            double Rr[9], Rn[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) Rr[j] = s.Rrel[(size_t)9 * p + j];
+            if ((reg >> a) & 1u) {
+                pg_mul<false>(Rr, rot + 9 * a, Rn);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) rot[9 * b + j] = Rn[j];
+                s.ldi[pg::I_REG] = (int)(reg | (1u << b));
+            } else {
+                pg_mul<true>(Rr, rot + 9 * b, Rn);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) rot[9 * a + j] = Rn[j];
+                s.ldi[pg::I_REG] = (int)(reg | (1u << a));
+            }
+            s.ldi[pg::I_TREE + step] = p;
+        }
+        sync();
+    }
+    sync();
+    const unsigned reg = (unsigned)s.ldi[pg::I_REG];
+    if (tid == 0) {
+        int n = 0;
+        s.ldi[pg::I_IDX] = -1;
+        for (int v = 1; v < mv::MAX_VIEWS; ++v) {
+            const bool in = (reg >> v) & 1u;
+            s.ldi[pg::I_IDX + v] = in ? n : -1;
+            if (in) { s.ldi[pg::I_VIEW + n] = v; ++n; }
+        }
+        s.ldi[pg::I_NR] = n;
+    }
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        if (k >= 0 && ((reg >> (k & 255)) & 1u) && ((reg >> ((k >> 8) & 255)) & 1u)) s.key[p] = k | pg::K_ACTIVE;
+    }
+    sync();
+}
+// r = 2 vec(q) of E, q of unit norm with a scalar part >= 0
+__device__ inline void pg_rot_residual(const double* E, double* r) {
+    const double tr = (E[0] + E[4]) + E[8];
+    double qw, qx, qy, qz;
+    if (tr > 0.0) {
+        const double h = sqrt(tr + 1.0) * 2.0;
+        qw = 0.25 * h; qx = (E[7] - E[5]) / h; qy = (E[2] - E[6]) / h; qz = (E[3] - E[1]) / h;
+    } else if (E[0] > E[4] && E[0] > E[8]) {
+        const double h = sqrt(((1.0 + E[0]) - E[4]) - E[8]) * 2.0;
+        qw = (E[7] - E[5]) / h; qx = 0.25 * h; qy = (E[1] + E[3]) / h; qz = (E[2] + E[6]) / h;
+    } else if (E[4] > E[8]) {
+        const double h = sqrt(((1.0 + E[4]) - E[0]) - E[8]) * 2.0;
+        qw = (E[2] - E[6]) / h; qx = (E[1] + E[3]) / h; qy = 0.25 * h; qz = (E[5] + E[7]) / h;
+    } else {
+        const double h = sqrt(((1.0 + E[8]) - E[0]) - E[4]) * 2.0;
+        qw = (E[3] - E[1]) / h; qx = (E[2] + E[6]) / h; qy = (E[5] + E[7]) / h; qz = 0.25 * h;
+    }
+    const double nq = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+    const double sg = qw < 0.0 ? -2.0 : 2.0;
+    r[0] = sg * (qx / nq); r[1] = sg * (qy / nq); r[2] = sg * (qz / nq);
+}
+// the residuals, factors and weights of the active edges at the rotations in LDS
+template <class Sync>
+__device__ inline void pg_rot_weights(const PgScene& s, int kind, int tid, int nt, const Sync& sync) {
+    const double* rot = s.lds + pg::L_ROT;
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        double f = 0.0, r[3] = {0.0, 0.0, 0.0};
+        if (k >= 0 && (k & pg::K_ACTIVE)) {
+            double Rr[9], M1[9], E[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) Rr[j] = s.Rrel[(size_t)9 * p + j];
+            pg_mul<false>(Rr, rot + 9 * (k & 255), M1);
+            pg_mul<true>(rot + 9 * ((k >> 8) & 255), M1, E);
+            pg_rot_residual(E, r);
+            f = pg_factor(sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]), s.crot, kind);
+        }
+        s.res[(size_t)3 * p] = r[0]; s.res[(size_t)3 * p + 1] = r[1]; s.res[(size_t)3 * p + 2] = r[2];
+        s.factor[(size_t)2 * p] = f;
+        s.wcur[p] = s.weight[p] * f;
+    }
+    sync();
+}
+// the view pair (i >= j, compact) of slot t of the packed triangle of blocks
+__device__ inline void pg_slot(int t, int& i, int& j) {
+    i = 0;
+    while (t > i) { t -= i + 1; ++i; }
+    j = t;
+}
+// the Laplacian of a rotation round and its three right-hand sides
+template <class Sync>
+__device__ inline void pg_rot_assemble(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const int nr = s.ldi[pg::I_NR];
+    double* T = s.lds + pg::L_SYS + pg::R_TRI;
+    double* rhs = s.lds + pg::L_SYS + pg::R_RHS;
+    for (int t = tid; t < nr * (nr + 1) / 2; t += nt) {
+        int i, j;
+        pg_slot(t, i, j);
+        const int vi = s.ldi[pg::I_VIEW + i], vj = s.ldi[pg::I_VIEW + j];
+        double acc = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0;
+        for (int p = 0; p < s.P; ++p) {
+            const int k = s.key[p];
+            if (k < 0 || !(k & pg::K_ACTIVE)) continue;
+            const int a = k & 255, b = (k >> 8) & 255;
+            if (i == j) {
+                if (a != vi && b != vi) continue;
+                const double w = s.wcur[p];
+                acc = acc + w;
+                const double r0 = w * s.res[(size_t)3 * p], r1 = w * s.res[(size_t)3 * p + 1], r2 = w * s.res[(size_t)3 * p + 2];
+                if (a == vi) { h0 = h0 - r0; h1 = h1 - r1; h2 = h2 - r2; }
+                else { h0 = h0 + r0; h1 = h1 + r1; h2 = h2 + r2; }
+            } else if ((a == vi && b == vj) || (a == vj && b == vi)) {
+                acc = acc - s.wcur[p];
+            }
+        }
+        T[i * (i + 1) / 2 + j] = acc;
+        if (i == j) { rhs[i] = h0; rhs[32 + i] = h1; rhs[64 + i] = h2; }
+    }
+    sync();
+}
+// the three solves of a rotation round (the solutions replace the right-hand sides) and the update of the rotations
+template <class Sync>
+__device__ inline void pg_rot_solve(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const int nr = s.ldi[pg::I_NR];
+    const double* T = s.lds + pg::L_SYS + pg::R_TRI;
+    double* Wk = s.lds + pg::L_SYS + pg::R_WORK;
+    double* rhs = s.lds + pg::L_SYS + pg::R_RHS;
+    double* piv = s.lds + pg::L_SYS + pg::R_PIV;
+    double* rot = s.lds + pg::L_ROT;
+    bool ok = true;
+    for (int x = 0; x < 3; ++x) {
+        for (int t = tid; t < nr * (nr + 1) / 2; t += nt) Wk[t] = T[t];
+        ok = ba_cholesky_solve(Wk, rhs + 32 * x, piv, nr, tid, nt, sync) && ok;
+        sync();
+    }
+    if (ok) {
+        for (int i = tid; i < nr; i += nt) {
+            const int v = s.ldi[pg::I_VIEW + i];
+            const double d6[6] = {rhs[i], rhs[32 + i], rhs[64 + i], 0.0, 0.0, 0.0}, t0[3] = {0.0, 0.0, 0.0};
+            double R[9], Rn[9], tn[3];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) R[j] = rot[9 * v + j];
+            ba_pose_update(R, t0, d6, Rn, tn);
+#pragma unroll
+            for (int j = 0; j < 9; ++j) rot[9 * v + j] = Rn[j];
+        }
+    }
+    sync();
+}
+// the directions of the active edges that have one
+template <class Sync>
+__device__ inline void pg_directions(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const double* rot = s.lds + pg::L_ROT;
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        double d[3] = {0.0, 0.0, 0.0};
+        if (k >= 0 && (k & pg::K_ACTIVE) && (k & pg::K_DIR)) {
+            const double t0 = s.trel[(size_t)3 * p], t1 = s.trel[(size_t)3 * p + 1], t2 = s.trel[(size_t)3 * p + 2];
+            const double n = sqrt((t0 * t0 + t1 * t1) + t2 * t2);
+            const double u0 = t0 / n, u1 = t1 / n, u2 = t2 / n;
+            const double* Rb = rot + 9 * ((k >> 8) & 255);
+#pragma unroll
+            for (int x = 0; x < 3; ++x) d[x] = (Rb[x] * u0 + Rb[3 + x] * u1) + Rb[6 + x] * u2;
+        }
+        s.dir[(size_t)3 * p] = d[0]; s.dir[(size_t)3 * p + 1] = d[1]; s.dir[(size_t)3 * p + 2] = d[2];
+    }
+    sync();
+}
+// the factors and weights of the position edges: 1 with `first`, else from the centres in LDS
+template <class Sync>
+__device__ inline void pg_pos_weights(const PgScene& s, int kind, bool first, int tid, int nt, const Sync& sync) {
+    const double* cen = s.lds + pg::L_CEN;
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        double f = 0.0;
+        if (k >= 0 && (k & pg::K_ACTIVE) && (k & pg::K_DIR)) {
+            f = 1.0;
+            if (!first) {
+                const double* ca = cen + 3 * (k & 255);
+                const double* cb = cen + 3 * ((k >> 8) & 255);
+                const double d0 = s.dir[(size_t)3 * p], d1 = s.dir[(size_t)3 * p + 1], d2 = s.dir[(size_t)3 * p + 2];
+                const double e0 = ca[0] - cb[0], e1 = ca[1] - cb[1], e2 = ca[2] - cb[2];
+                const double pr = (d0 * e0 + d1 * e1) + d2 * e2;
+                const double q0 = e0 - pr * d0, q1 = e1 - pr * d1, q2 = e2 - pr * d2;
+                const double rho = pr > 0.0 ? sqrt((q0 * q0 + q1 * q1) + q2 * q2) / sqrt((e0 * e0 + e1 * e1) + e2 * e2) : 1.0;
+                f = pg_factor(rho, s.cpos, kind);
+            }
+        }
+        s.factor[(size_t)2 * p + 1] = f;
+        s.wcur[p] = s.weight[p] * f;
+    }
+    sync();
+}
+// M (packed, n = 3 n_r) and g of a position round
+template <class Sync>
+__device__ inline void pg_pos_assemble(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const int nr = s.ldi[pg::I_NR];
+    double* T = s.lds + pg::L_SYS;
+    double* g = s.lds + pg::L_RHS;
+    for (int t = tid; t < nr * (nr + 1) / 2; t += nt) {
+        int i, j;
+        pg_slot(t, i, j);
+        const int vi = s.ldi[pg::I_VIEW + i], vj = s.ldi[pg::I_VIEW + j];
+        double B[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, h[3] = {0.0, 0.0, 0.0};
+        for (int p = 0; p < s.P; ++p) {
+            const int k = s.key[p];
+            if (k < 0 || !(k & pg::K_ACTIVE) || !(k & pg::K_DIR)) continue;
+            const int a = k & 255, b = (k >> 8) & 255;
+            const bool diag = i == j && (a == vi || b == vi), off = i != j && ((a == vi && b == vj) || (a == vj && b == vi));
+            if (!diag && !off) continue;
+            const double w = s.wcur[p];
+            const double d[3] = {s.dir[(size_t)3 * p], s.dir[(size_t)3 * p + 1], s.dir[(size_t)3 * p + 2]};
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+                for (int y = 0; y < 3; ++y) {
+                    const double m = w * ((x == y ? 1.0 : 0.0) - d[x] * d[y]);
+                    B[3 * x + y] = diag ? B[3 * x + y] + m : B[3 * x + y] - m;
+                }
+            if (diag) {
+#pragma unroll
+                for (int x = 0; x < 3; ++x) h[x] = a == vi ? h[x] + w * d[x] : h[x] - w * d[x];
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y)
+                if (i != j || y <= x) T[(3 * i + x) * (3 * i + x + 1) / 2 + 3 * j + y] = B[3 * x + y];
+        if (i == j) { g[3 * i] = h[0]; g[3 * i + 1] = h[1]; g[3 * i + 2] = h[2]; }
+    }
+    sync();
+}
+// A = M + (mu g) g', A c = g, the rigidity test, the scale; the centres of the views into LDS.  false: the positions are not determined
+template <class Sync>
+__device__ inline bool pg_pos_solve(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const int nr = s.ldi[pg::I_NR], n = 3 * nr;
+    double* T = s.lds + pg::L_SYS;
+    double* g = s.lds + pg::L_RHS;
+    double* piv = s.lds + pg::L_PIV;
+    double* dg = s.lds + pg::L_DIAG;
+    double* cen = s.lds + pg::L_CEN;
+    double* sc = s.lds + pg::L_SC;
+    if (tid == 0) {
+        double trm = 0.0, gg = 0.0;
+        for (int i = 0; i < n; ++i) { trm = trm + T[i * (i + 1) / 2 + i]; gg = gg + g[i] * g[i]; }
+        sc[0] = trm / gg;
+    }
+    sync();
+    const double mu = sc[0];
+    if (!(tv::is_finite(mu) && mu > 0.0)) return false;
+    for (int i = tid; i < n; i += nt) {
+        const double mg = mu * g[i];
+        for (int j = 0; j <= i; ++j) T[i * (i + 1) / 2 + j] = T[i * (i + 1) / 2 + j] + mg * g[j];
+        dg[i] = T[i * (i + 1) / 2 + i];
+    }
+    const bool ok = ba_cholesky_solve(T, g, piv, n, tid, nt, sync);
+    sync();
+    if (!ok) return false;
+    if (tid == 0) {
+        double lo = T[0] / dg[0];
+        for (int i = 1; i < n; ++i) {
+            const double q = T[i * (i + 1) / 2 + i] / dg[i];
+            lo = q < lo ? q : lo;
+        }
+        sc[1] = lo;
+    }
+    sync();
+    if (!(sc[1] >= s.min_ratio)) return false;
+    for (int i = tid; i < n; i += nt) cen[3 * s.ldi[pg::I_VIEW + i / 3] + i % 3] = g[i];
+    sync();
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        double a = 0.0, b = 0.0;
+        if (k >= 0 && (k & pg::K_ACTIVE) && (k & pg::K_DIR)) {
+            const double* ca = cen + 3 * (k & 255);
+            const double* cb = cen + 3 * ((k >> 8) & 255);
+            const double e0 = ca[0] - cb[0], e1 = ca[1] - cb[1], e2 = ca[2] - cb[2];
+            b = s.wcur[p];
+            a = b * ((s.dir[(size_t)3 * p] * e0 + s.dir[(size_t)3 * p + 1] * e1) + s.dir[(size_t)3 * p + 2] * e2);
+        }
+        s.ta[p] = a; s.tb[p] = b;
+    }
+    const double sa = pg_sum(s.ta, s.P, s.lds + pg::L_RED, tid, nt, sync);
+    const double sb = pg_sum(s.tb, s.P, s.lds + pg::L_RED, tid, nt, sync);
+    const double scale = sa / sb;
+    if (!(tv::is_finite(scale) && scale > 0.0)) return false;
+    for (int i = tid; i < n; i += nt) {
+        double* c = cen + 3 * s.ldi[pg::I_VIEW + i / 3] + i % 3;
+        *c = *c / scale;
+    }
+    sync();
+    return true;
+}
+// the counts of info: valid edges (0), with a direction (1), final rotation factor < 0.5 (2), final position factor < 0.5 (3)
+template <class Sync>
+__device__ inline int pg_count(const PgScene& s, int what, int tid, int nt, const Sync& sync) {
+    for (int p = tid; p < s.P; p += nt) {
+        const int k = s.key[p];
+        const bool act = k >= 0 && (k & pg::K_ACTIVE), dir = k >= 0 && (k & pg::K_DIR);
+        bool c = k >= 0;
+        if (what == 1) c = dir;
+        if (what == 2) c = act && s.factor[(size_t)2 * p] < 0.5;
+        if (what == 3) c = act && dir && s.factor[(size_t)2 * p + 1] < 0.5;
+        s.ta[p] = c ? 1.0 : 0.0;
+    }
+    return (int)pg_sum(s.ta, s.P, s.lds + pg::L_RED, tid, nt, sync);
+}
+// the whole scene
+template <class Sync>
+__device__ inline void pg_run(const PgScene& s, int tid, int nt, const Sync& sync) {
+    const double zero = s.min_ratio - s.min_ratio, nan = zero / zero;            // (NaN either way)
+    pg_keys(s, tid, nt, sync);
+    pg_tree(s, tid, nt, sync);
+    const int nr = s.ldi[pg::I_NR];
+    const unsigned reg = (unsigned)s.ldi[pg::I_REG];
+    const int last = pg_kind(s, s.iterations - 1);
+    bool pos = false;
+    if (nr > 0) {
+        for (int k = 0; k < s.iterations; ++k) {
+            pg_rot_weights(s, pg_kind(s, k), tid, nt, sync);
+            pg_rot_assemble(s, tid, nt, sync);
+            pg_rot_solve(s, tid, nt, sync);
+        }
+        pg_rot_weights(s, last, tid, nt, sync);
+        pg_directions(s, tid, nt, sync);
+        pos = true;
+        for (int k = 0; k < s.iterations && pos; ++k) {
+            pg_pos_weights(s, pg_kind(s, k), k == 0, tid, nt, sync);
+            pg_pos_assemble(s, tid, nt, sync);
+            pos = pg_pos_solve(s, tid, nt, sync);
+        }
+        if (pos) pg_pos_weights(s, last, false, tid, nt, sync);
+    } else {
+        for (int p = tid; p < s.P; p += nt) s.factor[(size_t)2 * p] = 0.0;
+    }
+    if (!pos) {
+        for (int p = tid; p < s.P; p += nt) s.factor[(size_t)2 * p + 1] = 0.0;
+        sync();
+    }
+    const int n_valid = pg_count(s, 0, tid, nt, sync), n_dir = pg_count(s, 1, tid, nt, sync);
+    const int n_rot = pg_count(s, 2, tid, nt, sync), n_pos = pos ? pg_count(s, 3, tid, nt, sync) : 0;
+    const double* rot = s.lds + pg::L_ROT;
+    const double* cen = s.lds + pg::L_CEN;
+    double* fin = s.lds + pg::L_BW;
+    for (int v = tid; v < s.V; v += nt) {
+        const bool in = (reg >> v) & 1u;
+        bool f = true;
+        const double* R = rot + 9 * v;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) { s.Rs[9 * v + j] = in ? R[j] : nan; f = f && tv::is_finite(R[j]); }
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const double t = -((R[3 * x] * cen[3 * v] + R[3 * x + 1] * cen[3 * v + 1]) + R[3 * x + 2] * cen[3 * v + 2]);
+            const bool has = in && (pos || v == 0);
+            s.ts[3 * v + x] = has ? (v == 0 ? 0.0 : t) : nan;
+            f = f && (!has || tv::is_finite(t));
+        }
+        fin[v] = in && !f ? 1.0 : 0.0;
+    }
+    sync();
+    if (tid == 0) {
+        bool bad = false;
+        int count = 0;
+        for (int v = 0; v < s.V; ++v) { bad = bad || fin[v] != 0.0; count += (int)((reg >> v) & 1u); }
+        s.registered[0] = (int32_t)reg;
+        s.info[0] = n_valid; s.info[1] = count; s.info[2] = n_dir; s.info[3] = n_rot; s.info[4] = n_pos; s.info[5] = 3 * nr;
+        s.info[6] = nr == 0 ? pg::ST_NOTHING : (bad ? pg::ST_NOT_FINITE : (pos ? pg::ST_OK : pg::ST_ROTATIONS_ONLY));
+        s.info[7] = 0;
+    }
+}
+// ---- pose graph end ----
+
+struct PgArgs {
+    const int32_t* pairs;     // (S, P, 2)
+    const double* Rrel;       // (S, P, 9)
+    const double* trel;       // (S, P, 3)
+    const double* weight;     // (S, P)
+    const int32_t* n_views;   // (S,) or NULL
+    int P, V, iterations, redescend;
+    double crot, cpos, min_ratio;
+    double* Rs;
+    double* ts;
+    int32_t* registered;
+    double* factor;
+    int32_t* info;
+    int32_t* key;             // workspace: (S, P) keys, then (S, 9, P) doubles
+    double* wd;
+};
+
+__global__ __launch_bounds__(256) void pose_graph_kernel(PgArgs a) {
+    __shared__ double lds[pg::L_END];
+    __shared__ int ldi[pg::I_END];
+    const size_t sc = blockIdx.x, P = (size_t)a.P;
+    int nv = a.n_views ? a.n_views[sc] : a.V;
+    nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
+    PgScene s;
+    s.pairs = a.pairs + sc * P * 2; s.Rrel = a.Rrel + sc * P * 9; s.trel = a.trel + sc * P * 3; s.weight = a.weight + sc * P;
+    s.nv = nv; s.P = a.P; s.V = a.V; s.iterations = a.iterations; s.redescend = a.redescend;
+    s.crot = a.crot; s.cpos = a.cpos; s.min_ratio = a.min_ratio;
+    s.Rs = a.Rs + sc * a.V * 9; s.ts = a.ts + sc * a.V * 3; s.registered = a.registered + sc; s.factor = a.factor + sc * P * 2; s.info = a.info + sc * 8;
+    s.key = a.key + sc * P;
+    double* w = a.wd + sc * 9 * P;
+    s.wcur = w; s.res = w + P; s.dir = w + 4 * P; s.ta = w + 7 * P; s.tb = w + 8 * P;
+    s.lds = lds; s.ldi = ldi;
+    pg_run(s, (int)threadIdx.x, 256, BaBarrier());
+}
+
+// the workspace's parts in order: the keys, the per-edge doubles
+static size_t pg_layout(int S, int P, size_t* off) {
+    const size_t sz[2] = {(size_t)S * P * 4, (size_t)S * P * 9 * 8};
+    size_t at = 0;
+    for (int i = 0; i < 2; ++i) { if (off) off[i] = at; at += ba_align(sz[i]); }
+    return at;
+}
+size_t pose_graph_workspace_bytes(int S, int P, int V) { (void)V; return pg_layout(S, P, nullptr); }
+
+int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
+                         int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
+                         double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* ws, hipStream_t st) {
+    if (S < 1 || S > 65535 || P < 1 || V < 2 || V > mv::MAX_VIEWS || iterations < 1 || redescend < 0 || redescend > iterations) return -1;
+    size_t off[2];
+    pg_layout(S, P, off);
+    char* w = static_cast<char*>(ws);
+    PgArgs a = {};
+    a.pairs = view_pairs; a.Rrel = R_rel; a.trel = t_rel; a.weight = weight; a.n_views = n_views; a.P = P; a.V = V; a.iterations = iterations;
+    a.redescend = redescend; a.crot = rot_scale_rad; a.cpos = pos_scale_sin; a.min_ratio = min_pivot_ratio;
+    a.Rs = Rs_out; a.ts = ts_out; a.registered = registered; a.factor = edge_factor; a.info = info;
+    a.key = reinterpret_cast<int32_t*>(w + off[0]); a.wd = reinterpret_cast<double*>(w + off[1]);
+    pose_graph_kernel<<<S, 256, 0, st>>>(a);
+    return 0;
+}
+
 }  // namespace xfh

@@ -144,6 +144,11 @@ int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, con
                          int S, int K, int V, const double* Ks, const double* Rs, const double* ts, unsigned fixed_views, int max_iterations,
                          double huber_px, double* Rs_out, double* ts_out, float* points3d_out, unsigned char* refined, int32_t* free_views, double* cost,
                          int32_t* info, void* ws, hipStream_t st);
+// (pose-graph initialisation: the world poses of the views from the relative poses of pairs: rotation and position averaging)
+size_t pose_graph_workspace_bytes(int S, int P, int V);
+int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
+                         int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
+                         double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* ws, hipStream_t st);
 // ---- k_tracks.hip (key-point tracks over a graph of view pairs: connected components of the match graph by a lock-free union-find) ----
 size_t track_graph_workspace_bytes(int S, int V, int K);
 int launch_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap, int V,

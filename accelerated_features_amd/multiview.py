@@ -14,6 +14,11 @@ With the matches of arbitrary pairs of views (a sequence's (v, v + 1), an unorde
 connected components of the match graph, ``triangulate_views_batch(anchor='first')`` triangulates each track from its lowest observing
 view, ``triangulate_graph_matches`` does both and ``view_points`` hands the map to ``estimate_absolute_pose_matches`` at any view's rows
 (``xfh_build_tracks_graph`` / ``xfh_triangulate_tracks``, csrc/k_tracks.hip).
+
+``average_poses_batch`` supplies the poses when nobody gives them: from the relative poses of the pairs (``relative_poses_graph_matches``
+runs ``estimate_relative_pose_matches`` over a pair graph) it estimates the world poses of all views -- a spanning tree, robust rotation
+averaging, robust position averaging on the directions (``xfh_average_poses``, csrc/k_triangulate.hip) -- and
+``reconstruct_graph_matches`` chains matches -> relative poses -> global poses -> tracks -> triangulation -> bundle adjustment.
 """
 import math
 
@@ -372,4 +377,177 @@ def view_points(points3d, track_of, view):
     if T:
         got = torch.gather(points3d.float(), 1, t.clamp(0, T - 1).unsqueeze(-1).expand(-1, -1, 3))
         out = torch.where(has.unsqueeze(-1), got, out)
+    return out
+
+
+# ---- pose-graph initialisation -----------------------------------------------------------------------------------------------
+PG_STATUS = ("ok", "nothing_at_view_0", "rotations_only", "not_finite")       # info[:, 6]
+PG_INFO_FIELDS = ("valid_edges", "registered_views", "direction_edges", "rotation_outliers", "position_outliers", "unknowns", "status", "spare")
+MAX_PG_ITERATIONS = 1000
+MAX_PG_PAIRS = 1 << 20
+# the geometric mean of the lowest pivot ratio of the rigid families (2.4e-2) and the highest of the non-rigid ones (1.8e-15)
+# on NOISE-FREE input.  At 0.5 degrees of noise the two families come within a factor of 1.3 (1.4e-3 against 1.1e-3): no value separates
+# them there, and two triangles that share one view pass as rigid.
+MIN_PIVOT_RATIO = 6.5e-9
+
+
+def _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio):
+    it, rd = int(iterations), int(redescend)
+    if not 1 <= it <= MAX_PG_ITERATIONS:
+        raise _lib.XFeatHipError(f"{who}: iterations {it} outside [1, {MAX_PG_ITERATIONS}]")
+    if not 0 <= rd <= it:
+        raise _lib.XFeatHipError(f"{who}: redescend {rd} outside [0, iterations = {it}]")
+    rot, pos, piv = float(rot_scale_deg), float(pos_scale_deg), float(min_pivot_ratio)
+    if not 0.0 < rot <= 180.0:
+        raise _lib.XFeatHipError(f"{who}: rot_scale_deg {rot} outside (0, 180]")
+    if not 0.0 < pos <= 90.0:
+        raise _lib.XFeatHipError(f"{who}: pos_scale_deg {pos} outside (0, 90]")
+    if not 0.0 <= piv < 1.0:
+        raise _lib.XFeatHipError(f"{who}: min_pivot_ratio {piv} outside [0, 1)")
+    return it, rd, math.radians(rot), math.sin(math.radians(pos)), piv
+
+
+def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30, redescend=10, rot_scale_deg=2.0, pos_scale_deg=2.0,
+                        min_pivot_ratio=MIN_PIVOT_RATIO, V=None):
+    """The world -> camera poses of the views of S scenes from the relative poses of P pairs of views per scene, in one call.
+
+    view_pairs   : (S, P, 2) or (P, 2) int32: edge p = (a, b)
+    R_rel, t_rel : (S, P, 3, 3), (S, P, 3) float64 with x_b = R_rel x_a + t_rel: what ``estimate_relative_pose_*`` returns with image 0 = a;
+                   only the direction of t_rel is used;  weight (S, P) >= 0, for example the inlier count
+    n_views      : V <= 32 as an int, or (S,) int32 (scene s uses its first n_views[s] views) with V given by the keyword
+    An edge is valid when a != b, both views are in [0, n_views), the weight is finite and > 0 and R_rel is finite; it has a direction when
+    t_rel is finite and not zero.  Duplicate pairs and pairs given as (b, a) are edges of their own.  A spanning tree from view 0 (largest
+    weight first) starts the rotations; `iterations` rounds of rotation averaging and as many of position averaging follow, the last
+    `redescend` of them with Cauchy's factor, the others with Huber's, at rot_scale_deg / pos_scale_deg.  Gauge: R_0 = I, c_0 = 0, the
+    weighted mean of the baselines projected on their directions is 1.  A view that the valid edges do not connect to view 0 is
+    unregistered: NaN pose, bit clear.  When the graph is not parallel-rigid (a chain of pairs (v, v + 1) is not: its baselines have no
+    common scale) the positions are not determined: status 2, 'Rs' valid, 'ts' NaN but for view 0.
+    Returns a dict of CUDA tensors: 'Rs' (S,V,3,3), 'ts' (S,V,3) float64, 'registered' (S,) int32 mask, 'edge_factor' (S,P,2) float64 (the
+    final rotation and position factors; 0 for an edge that took no part), 'info' (S,8) int32 (PG_INFO_FIELDS; status: PG_STATUS).
+    Asynchronous."""
+    who = "average_poses_batch"
+    it, rd, crot, cpos, piv = _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio)
+    view_pairs, R_rel, t_rel, weight = torch.as_tensor(view_pairs), torch.as_tensor(R_rel), torch.as_tensor(t_rel), torch.as_tensor(weight)
+    if R_rel.dim() != 4 or R_rel.shape[2:] != (3, 3):
+        raise RuntimeError('expected R_rel (S,P,3,3)')
+    S, P = R_rel.shape[:2]
+    if t_rel.shape != (S, P, 3) or weight.shape != (S, P):
+        raise RuntimeError('expected t_rel (S,P,3) and weight (S,P)')
+    if view_pairs.shape not in ((S, P, 2), (P, 2)):
+        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    per_scene = torch.is_tensor(n_views)
+    if per_scene:
+        if V is None:
+            raise RuntimeError('n_views per scene needs the keyword V')
+        if n_views.shape != (S,):
+            raise RuntimeError('n_views must have one entry per scene')
+    V = int(n_views) if not per_scene else int(V)
+    _views(who, V)
+    if P > MAX_PG_PAIRS:
+        raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_PG_PAIRS}")
+    dev = R_rel.device if R_rel.is_cuda else _twoview.device("pose-graph initialisation")
+    if view_pairs.dim() == 2:
+        view_pairs = view_pairs.expand(S, P, 2)
+    view_pairs = view_pairs.to(dev).to(torch.int32).contiguous()
+    R_rel, t_rel, weight = (x.to(dev).to(torch.float64).contiguous() for x in (R_rel, t_rel, weight))
+    n_views = n_views.to(dev).to(torch.int32).contiguous() if per_scene else None
+    Rs = torch.empty((S, V, 3, 3), dtype=torch.float64, device=dev)
+    ts = torch.empty((S, V, 3), dtype=torch.float64, device=dev)
+    registered = torch.empty((S,), dtype=torch.int32, device=dev)
+    factor = torch.empty((S, P, 2), dtype=torch.float64, device=dev)
+    info = torch.empty((S, 8), dtype=torch.int32, device=dev)
+    out = {'Rs': Rs, 'ts': ts, 'registered': registered, 'edge_factor': factor, 'info': info}
+    if S == 0 or P == 0:                      # no edge at all: written like the kernel writes a scene without a valid edge
+        Rs.fill_(float('nan')); ts.fill_(float('nan')); registered.fill_(1); info.zero_()
+        Rs[:, 0] = torch.eye(3, dtype=torch.float64, device=dev); ts[:, 0] = 0.0
+        info[:, 1] = 1; info[:, 6] = 1
+        return out
+    lib = _lib.load()
+
+    def call(a, b, ws, ws_bytes, stream):
+        return lib.xfh_average_poses(_ptr(view_pairs[a:b]), _ptr(R_rel[a:b]), _ptr(t_rel[a:b]), _ptr(weight[a:b]),
+                                     _ptr(n_views[a:b]) if n_views is not None else None, b - a, P, V, it, rd, crot, cpos, piv, _ptr(Rs[a:b]),
+                                     _ptr(ts[a:b]), _ptr(registered[a:b]), _ptr(factor[a:b]), _ptr(info[a:b]), ws, ws_bytes, stream)
+    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
+        _twoview.run_chunked("xfh_average_poses", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_pose_graph_workspace_bytes(n, P, V), dev,
+                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    return out
+
+
+def relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, min_inliers=15, **ransac):
+    """The relative poses of the pairs of a pair graph: ``estimate_relative_pose_matches`` once over the S P pairs of S scenes.
+
+    kpts (S,V,K,2) float32, view_pairs (S,P,2) or (P,2) int32, idx_a / idx_b (S,P,cap) int64, n_matches (S,P) int32 CUDA tensors as for
+    ``build_tracks_graph``; Ks (S,V,3,3) float64; **ransac: the estimator's settings (max_epipolar_error, success_prob, min_iterations,
+    max_iterations, seed).  The key-point tables and intrinsics of each pair are gathered by indexing (2 S P K points: choose S to fit).
+    Returns a dict: 'R_rel' (S,P,3,3), 't_rel' (S,P,3) float64 with x_b = R_rel x_a + t_rel, 'weight' (S,P) float64 = the inlier count where
+    a pose was found with at least min_inliers inliers, else 0 (also for a pair with a == b or a view outside [0, V)), 'inliers' (S,P,cap)
+    uint8, 'info' (S,P,8) int32 (pose.INFO_FIELDS): the arguments of ``average_poses_batch``.  Asynchronous."""
+    from . import pose
+    who = "relative_poses_graph_matches"
+    for t in (kpts, view_pairs, idx_a, idx_b, n_matches):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f'{who}: tensors expected')
+    if kpts.dim() != 4 or kpts.shape[3] != 2:
+        raise RuntimeError('expected kpts (S,V,K,2)')
+    S, V, K = kpts.shape[:3]
+    _views(who, V)
+    if idx_a.dim() != 3 or idx_a.shape[0] != S or idx_b.shape != idx_a.shape or n_matches.shape != idx_a.shape[:2]:
+        raise RuntimeError('expected idx_a, idx_b (S,P,cap) and n_matches (S,P) for kpts (S,V,K,2)')
+    P, cap = idx_a.shape[1:]
+    if view_pairs.shape not in ((S, P, 2), (P, 2)):
+        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    if int(min_inliers) < 0:
+        raise _lib.XFeatHipError(f"{who}: min_inliers {min_inliers} is negative")
+    if not kpts.is_cuda:
+        raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
+    dev = kpts.device
+    Ks = _f64(Ks, (S, V, 3, 3), dev, 'Ks')
+    vp = (view_pairs.expand(S, P, 2) if view_pairs.dim() == 2 else view_pairs).to(dev).long()
+    a, b = vp[..., 0], vp[..., 1]
+    legal = (a != b) & (a >= 0) & (a < V) & (b >= 0) & (b < V)
+    a, b = a.clamp(0, V - 1), b.clamp(0, V - 1)
+    sc = torch.arange(S, device=dev).unsqueeze(1).expand(S, P)
+    r = pose.estimate_relative_pose_matches(kpts[sc, a].reshape(S * P, K, 2).float().contiguous(), kpts[sc, b].reshape(S * P, K, 2).float().contiguous(),
+                                            idx_a.reshape(S * P, cap).contiguous(), idx_b.reshape(S * P, cap).contiguous(),
+                                            n_matches.reshape(S * P).contiguous(), Ks[sc, a].reshape(S * P, 3, 3), Ks[sc, b].reshape(S * P, 3, 3), **ransac)
+    info = r['info'].reshape(S, P, 8)
+    found = legal & (info[..., 0] != 0) & (info[..., 3] >= int(min_inliers))
+    weight = torch.where(found, info[..., 3].double(), torch.zeros((), dtype=torch.float64, device=dev))
+    return {'R_rel': r['R'].reshape(S, P, 3, 3), 't_rel': r['t'].reshape(S, P, 3), 'weight': weight, 'inliers': r['inliers'].reshape(S, P, cap),
+            'info': info}
+
+
+def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks, min_inliers=15, ransac=None, iterations=30, redescend=10,
+                              rot_scale_deg=2.0, pos_scale_deg=2.0, min_pivot_ratio=MIN_PIVOT_RATIO, max_reproj_error=4.0, min_parallax_deg=1.0,
+                              max_depth=float('inf'), min_views=2, min_length=2, max_tracks=None, fixed_views=1, max_iterations=10, huber_px=1.0):
+    """From the matches of an unordered set of images to a map: ``relative_poses_graph_matches`` -> ``average_poses_batch`` ->
+    ``triangulate_graph_matches`` -> ``bundle_adjust_batch`` -> ``triangulate_views_batch(anchor='first')`` under the refined poses.
+
+    kpts (S,V,K,2), view_pairs (S,P,2) or (P,2), idx_a / idx_b (S,P,cap), n_matches (S,P) CUDA tensors; n_views (S,) int32 or None = all V;
+    Ks (S,V,3,3); ransac: a dict of the relative-pose settings; the other keywords are those of the stages.
+    The NaN pose of a view that the pose graph did not register (and every pose but view 0's of a scene with status 2) passes through
+    untouched: both triangulations treat such a view as one that observes nothing (a pose that is not usable), the adjustment holds it.
+    Returns the second triangulation's dict with 'Rs', 'ts' (the refined poses), 'refined', 'free_views', 'cost', 'ba_info' of the
+    adjustment, 'tracks', 'track_of', 'n_tracks', 'track_info' of the tables, 'Rs_init', 'ts_init', 'registered', 'edge_factor', 'pg_info' of
+    the pose graph and 'R_rel', 't_rel', 'weight', 'rel_info' of the pairs added.  Asynchronous: nothing synchronises with the host."""
+    who = "reconstruct_graph_matches"
+    _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio)
+    _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
+    _ba_settings(who, fixed_views, max_iterations, huber_px)
+    rel = relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, min_inliers, **(ransac or {}))
+    V = kpts.shape[1]
+    pg = average_poses_batch(view_pairs, rel['R_rel'], rel['t_rel'], rel['weight'], V if n_views is None else torch.as_tensor(n_views), iterations,
+                             redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio, V=V)
+    vp = view_pairs.to(kpts.device).to(torch.int32).contiguous()
+    first = triangulate_graph_matches(kpts, vp, idx_a, idx_b, n_matches, n_views, Ks, pg['Rs'], pg['ts'], max_reproj_error, min_parallax_deg, max_depth,
+                                      min_views, min_length, max_tracks)
+    ba = bundle_adjust_batch(kpts, first['tracks'], first['inlier_views'], first['points3d'], n_views, Ks, pg['Rs'], pg['ts'], fixed_views,
+                             max_iterations, huber_px)
+    out = triangulate_views_batch(kpts, first['tracks'], n_views, Ks, ba['Rs'], ba['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views,
+                                  anchor='first')
+    out.update(Rs=ba['Rs'], ts=ba['ts'], refined=ba['refined'], free_views=ba['free_views'], cost=ba['cost'], ba_info=ba['info'],
+               tracks=first['tracks'], track_of=first['track_of'], n_tracks=first['n_tracks'], track_info=first['track_info'],
+               Rs_init=pg['Rs'], ts_init=pg['ts'], registered=pg['registered'], edge_factor=pg['edge_factor'], pg_info=pg['info'],
+               R_rel=rel['R_rel'], t_rel=rel['t_rel'], weight=rel['weight'], rel_info=rel['info'])
     return out

@@ -582,6 +582,36 @@ int xfh_bundle_adjust(const float* kpts, int kpt_cap, const int32_t* tracks, con
                       size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pose-graph initialisation: the world -> camera poses of the V <= 32 views of S scenes from the relative poses of P pairs of
+ * views per scene: a spanning tree, robust rotation averaging and robust position averaging on the directions (DESIGN.md 3.19 /
+ * csrc/k_triangulate.hip).  One launch, one workgroup per scene; asynchronous; no host synchronisation inside; two calls give
+ * the same bits.  Every argument check returns before any launch.
+ *   view_pairs (S,P,2) int32; edge p = (a, b) carries R_rel (S,P,3,3) and t_rel (S,P,3) fp64 with x_b = R_rel x_a + t_rel (what
+ *   xfh_estimate_relpose returns with image 0 = a; only the direction of t_rel is used) and weight (S,P) fp64 >= 0.  n_views (S,)
+ *   int32 or NULL = V.  An edge is valid when a != b, both views are in [0, n_views), the weight is finite and > 0 and R_rel is
+ *   finite; it has a direction when t_rel is finite and not zero.  Duplicate pairs and pairs given as (b, a) are edges of their own.
+ *   iterations in [1, 1000] rounds of each solve, the last redescend of them with Cauchy's factor, the others with Huber's;
+ *   rot_scale_rad: the rotation residual's scale in radians; pos_scale_sin: the sine of the direction residual's scale;
+ *   min_pivot_ratio: the smallest pivot^2 / diagonal of the position system below which the graph counts as not parallel-rigid.
+ *   Gauge R_0 = I, c_0 = 0; the weighted mean of the baselines projected on their directions is 1.
+ *   Outputs: Rs_out (S,V,3,3), ts_out (S,V,3) fp64, NaN for a view that the edges do not connect to view 0; registered (S,) int32
+ *   mask of the connected views; edge_factor (S,P,2) fp64: the final rotation and position factors, 0 for an edge that took no
+ *   part; info (S,8) int32: valid edges, registered views, edges with a direction, rotation edges with a final factor < 0.5,
+ *   position edges likewise, unknowns of the position solve, status (XFH_PG_*), 0.  XFH_PG_NOTHING: no valid edge at view 0;
+ *   XFH_PG_ROTATIONS_ONLY: the positions are not determined (Rs_out valid, ts_out of every view but 0 NaN);
+ *   XFH_PG_NOT_FINITE: an output is not finite.  workspace: xfh_pose_graph_workspace_bytes(S, P, V) bytes, 256-byte aligned (0: bad shape).
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_PG_OK 0
+#define XFH_PG_NOTHING 1
+#define XFH_PG_ROTATIONS_ONLY 2
+#define XFH_PG_NOT_FINITE 3
+size_t xfh_pose_graph_workspace_bytes(int S, int P, int V);
+int xfh_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight,
+                      const int32_t* n_views, int S, int P, int V, int iterations, int redescend, double rot_scale_rad,
+                      double pos_scale_sin, double min_pivot_ratio, double* Rs_out, double* ts_out, int32_t* registered,
+                      double* edge_factor, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
