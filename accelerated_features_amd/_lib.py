@@ -84,6 +84,11 @@ SIGNATURES = {
     "xfh_bundle_adjust": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, C.c_uint32, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_pose_graph_workspace_bytes": (_sz, [_i, _i, _i]),
     "xfh_average_poses": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_baseline_ratios_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "xfh_baseline_ratios": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_pose_graph_ratios_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_average_poses_ratios": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _sz,
+                                      _p]),
     "xfh_fundamental_workspace_bytes": (_sz, [_i, _i]),
     "xfh_find_fundamental": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "xfh_find_fundamental_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz,

@@ -1284,6 +1284,68 @@ int xfh_average_poses(const int32_t* view_pairs, const double* R_rel, const doub
     return check_launch(who);
 }
 
+// ---- baseline scales from shared tracks (posescale_body.hpp): every check returns before any launch
+size_t xfh_baseline_ratios_workspace_bytes(int S, int P, int V, int K) {
+    if (S <= 0 || S > 65535 || P <= 0 || P > 512 || V < 2 || V > 32 || K <= 0 || K > 4096) return 0;
+    return 256;                                            // (the kernel works in LDS; a size of 0 would read as a bad shape)
+}
+
+int xfh_baseline_ratios(const float* kpts, const int32_t* tracks, const int32_t* track_of, const int32_t* view_pairs, const double* R_rel,
+                        const double* t_rel, const double* weight, const double* Ks, const int32_t* n_views, int S, int P, int V, int K, int T,
+                        double max_reproj_error, double cos_min, double max_depth, int min_common, double* ratio, int32_t* count,
+                        int32_t* shared_view, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    const char* who = "xfh_baseline_ratios";
+    if (!kpts || !tracks || !track_of || !view_pairs || !R_rel || !t_rel || !weight || !Ks || !ratio || !count || !shared_view || !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (P < 1 || P > 512) return fail(XFH_ERR_ARG, "%s: P %d outside [1, 512]", who, P);
+    if (K < 1 || K > 4096) return fail(XFH_ERR_ARG, "%s: K %d outside [1, 4096]", who, K);
+    if (T < 1 || T > V * K) return fail(XFH_ERR_ARG, "%s: T %d outside [1, V K = %d]", who, T, V * K);
+    if (!(max_reproj_error > 0.0)) return fail(XFH_ERR_ARG, "%s: max_reproj_error %g must be positive", who, max_reproj_error);
+    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return fail(XFH_ERR_ARG, "%s: cos_min %g outside [-1, 1]", who, cos_min);
+    if (!(max_depth > 0.0)) return fail(XFH_ERR_ARG, "%s: max_depth %g must be positive (+inf: no limit)", who, max_depth);
+    if (min_common < 1) return fail(XFH_ERR_ARG, "%s: min_common %d below 1", who, min_common);
+    int rc = check_ws(workspace, workspace_bytes, 256);
+    if (rc) return rc;
+    if (launch_baseline_ratios(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weight, Ks, n_views, S, P, V, K, T, max_reproj_error, cos_min, max_depth,
+                               min_common, ratio, count, shared_view, info, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
+size_t xfh_pose_graph_ratios_workspace_bytes(int S, int P, int V) {
+    if (S <= 0 || S > 65535 || P <= 0 || P > 512 || V < 2 || V > 32) return 0;
+    return xfh::pose_graph_ratios_workspace_bytes(S, P, V);
+}
+
+int xfh_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views,
+                             const double* ratio, const int32_t* ratio_count, int S, int P, int V, int iterations, int redescend, double rot_scale_rad,
+                             double pos_scale_sin, double min_pivot_ratio, double scale_weight, double scale_tol, double* Rs_out, double* ts_out,
+                             int32_t* registered, double* edge_factor, double* ratio_factor, int32_t* info, void* workspace, size_t workspace_bytes,
+                             xfh_stream stream) {
+    const char* who = "xfh_average_poses_ratios";
+    if (!view_pairs || !R_rel || !t_rel || !weight || !ratio || !ratio_count || !Rs_out || !ts_out || !registered || !edge_factor || !ratio_factor || !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2 || V > 32) return fail(XFH_ERR_ARG, "%s: V %d outside [2, 32]", who, V);
+    if (P < 1 || P > 512) return fail(XFH_ERR_ARG, "%s: P %d outside [1, 512]", who, P);
+    if (iterations < 1 || iterations > 1000) return fail(XFH_ERR_ARG, "%s: iterations %d outside [1, 1000]", who, iterations);
+    if (redescend < 0 || redescend > iterations) return fail(XFH_ERR_ARG, "%s: redescend %d outside [0, iterations]", who, redescend);
+    if (!(rot_scale_rad > 0.0) || !(rot_scale_rad < 4.0)) return fail(XFH_ERR_ARG, "%s: rot_scale_rad %g outside (0, 4)", who, rot_scale_rad);
+    if (!(pos_scale_sin > 0.0) || !(pos_scale_sin <= 1.0)) return fail(XFH_ERR_ARG, "%s: pos_scale_sin %g outside (0, 1]", who, pos_scale_sin);
+    if (!(min_pivot_ratio >= 0.0) || !(min_pivot_ratio < 1.0)) return fail(XFH_ERR_ARG, "%s: min_pivot_ratio %g outside [0, 1)", who, min_pivot_ratio);
+    if (!(scale_weight > 0.0) || !(scale_weight < 1e300)) return fail(XFH_ERR_ARG, "%s: scale_weight %g must be positive and finite", who, scale_weight);
+    if (!(scale_tol > 0.0) || !(scale_tol <= 1.0)) return fail(XFH_ERR_ARG, "%s: scale_tol %g outside (0, 1]", who, scale_tol);
+    int rc = check_ws(workspace, workspace_bytes, xfh::pose_graph_ratios_workspace_bytes(S, P, V));
+    if (rc) return rc;
+    if (launch_average_poses_ratios(view_pairs, R_rel, t_rel, weight, n_views, ratio, ratio_count, S, P, V, iterations, redescend, rot_scale_rad,
+                                    pos_scale_sin, min_pivot_ratio, scale_weight, scale_tol, Rs_out, ts_out, registered, edge_factor, ratio_factor, info,
+                                    workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

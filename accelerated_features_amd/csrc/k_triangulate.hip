@@ -1540,6 +1540,8 @@ int launch_bundle_adjust(const float* kpts, int kcap, const int32_t* tracks, con
 // the rotations and centres (3 KB), the sums' and the tree's selection buffers.  Per-edge keys, weights, residuals, directions and the
 // sums' terms live in the workspace (pose_graph_workspace_bytes).
 
+// pg_run is pg_run_with(PgEdgesOnly): the position rounds call the hooks of a Terms argument (prepare, weights, assemble, finish), empty here; the
+// baseline ratios of posescale_body.hpp are the other Terms.
 // ---- pose graph begin (host-compilable: tests/test_posegraph_emulated.py slices it out behind the three slices above) ----
 namespace pg {
 constexpr int ST_OK = 0, ST_NOTHING = 1, ST_ROTATIONS_ONLY = 2, ST_NOT_FINITE = 3;
@@ -1610,20 +1612,22 @@ __device__ inline void pg_mul(const double* A, const double* B, double* C) {
         for (int j = 0; j < 3; ++j)
             C[3 * i + j] = TA ? (A[i] * B[j] + A[3 + i] * B[3 + j]) + A[6 + i] * B[6 + j] : (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
 }
-// the keys of the edges: valid, views, direction
+// the key of edge p: valid, views, direction
+__device__ inline int pg_edge_key(const int32_t* pairs, const double* Rrel, const double* trel, const double* weight, int nv, int p) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    const double w = weight[p];
+    bool ok = a != b && a >= 0 && a < nv && b >= 0 && b < nv && tv::is_finite(w) && w > 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ok = ok && tv::is_finite(Rrel[(size_t)9 * p + k]);
+    const double t0 = trel[(size_t)3 * p], t1 = trel[(size_t)3 * p + 1], t2 = trel[(size_t)3 * p + 2];
+    const double n2 = (t0 * t0 + t1 * t1) + t2 * t2;
+    const bool dir = tv::is_finite(t0) && tv::is_finite(t1) && tv::is_finite(t2) && tv::is_finite(n2) && n2 > 0.0;
+    return ok ? (a | (b << 8) | (dir ? pg::K_DIR : 0)) : -1;
+}
+// the keys of the edges
 template <class Sync>
 __device__ inline void pg_keys(const PgScene& s, int tid, int nt, const Sync& sync) {
-    for (int p = tid; p < s.P; p += nt) {
-        const int a = s.pairs[2 * p], b = s.pairs[2 * p + 1];
-        const double w = s.weight[p];
-        bool ok = a != b && a >= 0 && a < s.nv && b >= 0 && b < s.nv && tv::is_finite(w) && w > 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) ok = ok && tv::is_finite(s.Rrel[(size_t)9 * p + k]);
-        const double t0 = s.trel[(size_t)3 * p], t1 = s.trel[(size_t)3 * p + 1], t2 = s.trel[(size_t)3 * p + 2];
-        const double n2 = (t0 * t0 + t1 * t1) + t2 * t2;
-        const bool dir = tv::is_finite(t0) && tv::is_finite(t1) && tv::is_finite(t2) && tv::is_finite(n2) && n2 > 0.0;
-        s.key[p] = ok ? (a | (b << 8) | (dir ? pg::K_DIR : 0)) : -1;
-    }
+    for (int p = tid; p < s.P; p += nt) s.key[p] = pg_edge_key(s.pairs, s.Rrel, s.trel, s.weight, s.nv, p);
     sync();
 }
 // the spanning tree: rotations of the reached views in LDS, the mask, the compact numbering; marks the active edges
@@ -1969,12 +1973,20 @@ __device__ inline int pg_count(const PgScene& s, int what, int tid, int nt, cons
     }
     return (int)pg_sum(s.ta, s.P, s.lds + pg::L_RED, tid, nt, sync);
 }
+// what the position rounds add to the edges' terms: nothing (pg_run), or the baseline ratios of posescale_body.hpp (pg_run_ratios)
+struct PgEdgesOnly {
+    template <class Sync> __device__ inline void prepare(const PgScene&, int, int, const Sync&) const {}
+    template <class Sync> __device__ inline void weights(const PgScene&, int, bool, int, int, const Sync&) const {}
+    template <class Sync> __device__ inline void assemble(const PgScene&, int, int, const Sync&) const {}
+    template <class Sync> __device__ inline void finish(const PgScene&, bool, int, int, const Sync&) const {}
+};
 // the whole scene
-template <class Sync>
-__device__ inline void pg_run(const PgScene& s, int tid, int nt, const Sync& sync) {
+template <class Sync, class Terms>
+__device__ inline void pg_run_with(const PgScene& s, const Terms& x, int tid, int nt, const Sync& sync) {
     const double zero = s.min_ratio - s.min_ratio, nan = zero / zero;            // (NaN either way)
     pg_keys(s, tid, nt, sync);
     pg_tree(s, tid, nt, sync);
+    x.prepare(s, tid, nt, sync);
     const int nr = s.ldi[pg::I_NR];
     const unsigned reg = (unsigned)s.ldi[pg::I_REG];
     const int last = pg_kind(s, s.iterations - 1);
@@ -1990,13 +2002,19 @@ __device__ inline void pg_run(const PgScene& s, int tid, int nt, const Sync& syn
         pos = true;
         for (int k = 0; k < s.iterations && pos; ++k) {
             pg_pos_weights(s, pg_kind(s, k), k == 0, tid, nt, sync);
+            x.weights(s, pg_kind(s, k), k == 0, tid, nt, sync);
             pg_pos_assemble(s, tid, nt, sync);
+            x.assemble(s, tid, nt, sync);
             pos = pg_pos_solve(s, tid, nt, sync);
         }
-        if (pos) pg_pos_weights(s, last, false, tid, nt, sync);
+        if (pos) {
+            pg_pos_weights(s, last, false, tid, nt, sync);
+            x.weights(s, last, false, tid, nt, sync);
+        }
     } else {
         for (int p = tid; p < s.P; p += nt) s.factor[(size_t)2 * p] = 0.0;
     }
+    x.finish(s, pos, tid, nt, sync);
     if (!pos) {
         for (int p = tid; p < s.P; p += nt) s.factor[(size_t)2 * p + 1] = 0.0;
         sync();
@@ -2032,6 +2050,8 @@ __device__ inline void pg_run(const PgScene& s, int tid, int nt, const Sync& syn
         s.info[7] = 0;
     }
 }
+template <class Sync>
+__device__ inline void pg_run(const PgScene& s, int tid, int nt, const Sync& sync) { pg_run_with(s, PgEdgesOnly(), tid, nt, sync); }
 // ---- pose graph end ----
 
 struct PgArgs {
@@ -2051,10 +2071,9 @@ struct PgArgs {
     double* wd;
 };
 
-__global__ __launch_bounds__(256) void pose_graph_kernel(PgArgs a) {
-    __shared__ double lds[pg::L_END];
-    __shared__ int ldi[pg::I_END];
-    const size_t sc = blockIdx.x, P = (size_t)a.P;
+// scene sc of a call; lds: pg::L_END doubles, ldi: pg::I_END ints
+__device__ inline PgScene pg_scene_of(const PgArgs& a, size_t sc, double* lds, int* ldi) {
+    const size_t P = (size_t)a.P;
     int nv = a.n_views ? a.n_views[sc] : a.V;
     nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
     PgScene s;
@@ -2066,7 +2085,13 @@ __global__ __launch_bounds__(256) void pose_graph_kernel(PgArgs a) {
     double* w = a.wd + sc * 9 * P;
     s.wcur = w; s.res = w + P; s.dir = w + 4 * P; s.ta = w + 7 * P; s.tb = w + 8 * P;
     s.lds = lds; s.ldi = ldi;
-    pg_run(s, (int)threadIdx.x, 256, BaBarrier());
+    return s;
+}
+
+__global__ __launch_bounds__(256) void pose_graph_kernel(PgArgs a) {
+    __shared__ double lds[pg::L_END];
+    __shared__ int ldi[pg::I_END];
+    pg_run(pg_scene_of(a, blockIdx.x, lds, ldi), (int)threadIdx.x, 256, BaBarrier());
 }
 
 // the workspace's parts in order: the keys, the per-edge doubles
@@ -2078,10 +2103,9 @@ static size_t pg_layout(int S, int P, size_t* off) {
 }
 size_t pose_graph_workspace_bytes(int S, int P, int V) { (void)V; return pg_layout(S, P, nullptr); }
 
-int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
-                         int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
-                         double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* ws, hipStream_t st) {
-    if (S < 1 || S > 65535 || P < 1 || V < 2 || V > mv::MAX_VIEWS || iterations < 1 || redescend < 0 || redescend > iterations) return -1;
+static PgArgs pg_args(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P, int V,
+                      int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out, double* ts_out,
+                      int32_t* registered, double* edge_factor, int32_t* info, void* ws) {
     size_t off[2];
     pg_layout(S, P, off);
     char* w = static_cast<char*>(ws);
@@ -2090,8 +2114,20 @@ int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const d
     a.redescend = redescend; a.crot = rot_scale_rad; a.cpos = pos_scale_sin; a.min_ratio = min_pivot_ratio;
     a.Rs = Rs_out; a.ts = ts_out; a.registered = registered; a.factor = edge_factor; a.info = info;
     a.key = reinterpret_cast<int32_t*>(w + off[0]); a.wd = reinterpret_cast<double*>(w + off[1]);
+    return a;
+}
+
+int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
+                         int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
+                         double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* ws, hipStream_t st) {
+    if (S < 1 || S > 65535 || P < 1 || V < 2 || V > mv::MAX_VIEWS || iterations < 1 || redescend < 0 || redescend > iterations) return -1;
+    const PgArgs a = pg_args(view_pairs, R_rel, t_rel, weight, n_views, S, P, V, iterations, redescend, rot_scale_rad, pos_scale_sin, min_pivot_ratio, Rs_out,
+                             ts_out, registered, edge_factor, info, ws);
     pose_graph_kernel<<<S, 256, 0, st>>>(a);
     return 0;
 }
+
+// the baseline ratios of the edge pairs that share a view and their terms in the position rounds
+#include "posescale_body.hpp"
 
 }  // namespace xfh

@@ -149,6 +149,17 @@ size_t pose_graph_workspace_bytes(int S, int P, int V);
 int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views, int S, int P,
                          int V, int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio, double* Rs_out,
                          double* ts_out, int32_t* registered, double* edge_factor, int32_t* info, void* ws, hipStream_t st);
+// (posescale_body.hpp, compiled with k_triangulate.hip: the baseline ratios of the edge pairs that share a view from the tracks, and the pose
+// graph with their terms in the position rounds)
+int launch_baseline_ratios(const float* kpts, const int32_t* tracks, const int32_t* track_of, const int32_t* view_pairs, const double* R_rel,
+                           const double* t_rel, const double* weight, const double* Ks, const int32_t* n_views, int S, int P, int V, int K, int T,
+                           double max_reproj_error, double cos_min, double max_depth, int min_common, double* ratio, int32_t* count,
+                           int32_t* shared_view, int32_t* info, hipStream_t st);
+size_t pose_graph_ratios_workspace_bytes(int S, int P, int V);
+int launch_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight, const int32_t* n_views,
+                                const double* ratio, const int32_t* ratio_count, int S, int P, int V, int iterations, int redescend, double rot_scale_rad,
+                                double pos_scale_sin, double min_pivot_ratio, double scale_weight, double scale_tol, double* Rs_out, double* ts_out,
+                                int32_t* registered, double* edge_factor, double* ratio_factor, int32_t* info, void* ws, hipStream_t st);
 // ---- k_tracks.hip (key-point tracks over a graph of view pairs: connected components of the match graph by a lock-free union-find) ----
 size_t track_graph_workspace_bytes(int S, int V, int K);
 int launch_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap, int V,

@@ -389,6 +389,11 @@ MAX_PG_PAIRS = 1 << 20
 # on NOISE-FREE input.  At 0.5 degrees of noise the two families come within a factor of 1.3 (1.4e-3 against 1.1e-3): no value separates
 # them there, and two triangles that share one view pass as rigid.
 MIN_PIVOT_RATIO = 6.5e-9
+# baseline scales from shared tracks
+MAX_RATIO_PAIRS = 512                        # ps::MAX_PAIRS: all 496 pairs of 32 views fit
+MAX_RATIO_KPTS = 4096                        # ps::MAX_K: the values of a wedge are selected in LDS
+SCALE_TOL = 0.1                              # measured on the restatement at 0.5 px / 0.5 degrees
+PS_INFO_FIELDS = ("wedges", "ratios", "tracks_examined", "tracks_valid", "status", "spare0", "spare1", "spare2")
 
 
 def _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio):
@@ -408,7 +413,7 @@ def _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_p
 
 
 def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30, redescend=10, rot_scale_deg=2.0, pos_scale_deg=2.0,
-                        min_pivot_ratio=MIN_PIVOT_RATIO, V=None):
+                        min_pivot_ratio=MIN_PIVOT_RATIO, V=None, ratio=None, ratio_count=None, scale_weight=1.0, scale_tol=SCALE_TOL):
     """The world -> camera poses of the views of S scenes from the relative poses of P pairs of views per scene, in one call.
 
     view_pairs   : (S, P, 2) or (P, 2) int32: edge p = (a, b)
@@ -422,11 +427,23 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
     weighted mean of the baselines projected on their directions is 1.  A view that the valid edges do not connect to view 0 is
     unregistered: NaN pose, bit clear.  When the graph is not parallel-rigid (a chain of pairs (v, v + 1) is not: its baselines have no
     common scale) the positions are not determined: status 2, 'Rs' valid, 'ts' NaN but for view 0.
+    ratio, ratio_count: (S, P, P) float64 / int32 of ``baseline_ratios_batch`` (both or neither; P <= 512): the baseline ratios of the edge
+    pairs that share a view join the position rounds with the weight scale_weight ratio_count and the robust scale scale_tol (the relative
+    disagreement |u_p - r u_q| / (u_p + r u_q) of the two baselines at which the factor starts to fall), which gives a chain positions.
+    None: the call and the bytes of the pose graph without them.
     Returns a dict of CUDA tensors: 'Rs' (S,V,3,3), 'ts' (S,V,3) float64, 'registered' (S,) int32 mask, 'edge_factor' (S,P,2) float64 (the
-    final rotation and position factors; 0 for an edge that took no part), 'info' (S,8) int32 (PG_INFO_FIELDS; status: PG_STATUS).
-    Asynchronous."""
+    final rotation and position factors; 0 for an edge that took no part), 'info' (S,8) int32 (PG_INFO_FIELDS; status: PG_STATUS) and, with
+    ratios, 'ratio_factor' (S,P,P) float64 (the final factor of every wedge that took part, else 0).  Asynchronous."""
     who = "average_poses_batch"
     it, rd, crot, cpos, piv = _pg_settings(who, iterations, redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio)
+    if (ratio is None) != (ratio_count is None):
+        raise RuntimeError('ratio and ratio_count come together')
+    if ratio is not None:
+        sw, stol = float(scale_weight), float(scale_tol)
+        if not 0.0 < sw < 1e300:
+            raise _lib.XFeatHipError(f"{who}: scale_weight {sw} must be positive and finite")
+        if not 0.0 < stol <= 1.0:
+            raise _lib.XFeatHipError(f"{who}: scale_tol {stol} outside (0, 1]")
     view_pairs, R_rel, t_rel, weight = torch.as_tensor(view_pairs), torch.as_tensor(R_rel), torch.as_tensor(t_rel), torch.as_tensor(weight)
     if R_rel.dim() != 4 or R_rel.shape[2:] != (3, 3):
         raise RuntimeError('expected R_rel (S,P,3,3)')
@@ -457,6 +474,14 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
     factor = torch.empty((S, P, 2), dtype=torch.float64, device=dev)
     info = torch.empty((S, 8), dtype=torch.int32, device=dev)
     out = {'Rs': Rs, 'ts': ts, 'registered': registered, 'edge_factor': factor, 'info': info}
+    if ratio is not None:
+        ratio, ratio_count = torch.as_tensor(ratio), torch.as_tensor(ratio_count)
+        if ratio.shape != (S, P, P) or ratio_count.shape != (S, P, P):
+            raise RuntimeError('expected ratio and ratio_count (S,P,P)')
+        if P > MAX_RATIO_PAIRS:
+            raise _lib.XFeatHipError(f"{who}: {P} pairs with ratios, more than {MAX_RATIO_PAIRS}")
+        ratio, ratio_count = ratio.to(dev).to(torch.float64).contiguous(), ratio_count.to(dev).to(torch.int32).contiguous()
+        out['ratio_factor'] = rfactor = torch.zeros((S, P, P), dtype=torch.float64, device=dev)
     if S == 0 or P == 0:                      # no edge at all: written like the kernel writes a scene without a valid edge
         Rs.fill_(float('nan')); ts.fill_(float('nan')); registered.fill_(1); info.zero_()
         Rs[:, 0] = torch.eye(3, dtype=torch.float64, device=dev); ts[:, 0] = 0.0
@@ -468,8 +493,91 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
         return lib.xfh_average_poses(_ptr(view_pairs[a:b]), _ptr(R_rel[a:b]), _ptr(t_rel[a:b]), _ptr(weight[a:b]),
                                      _ptr(n_views[a:b]) if n_views is not None else None, b - a, P, V, it, rd, crot, cpos, piv, _ptr(Rs[a:b]),
                                      _ptr(ts[a:b]), _ptr(registered[a:b]), _ptr(factor[a:b]), _ptr(info[a:b]), ws, ws_bytes, stream)
+    def call_ratios(a, b, ws, ws_bytes, stream):
+        return lib.xfh_average_poses_ratios(_ptr(view_pairs[a:b]), _ptr(R_rel[a:b]), _ptr(t_rel[a:b]), _ptr(weight[a:b]),
+                                            _ptr(n_views[a:b]) if n_views is not None else None, _ptr(ratio[a:b]), _ptr(ratio_count[a:b]), b - a, P, V,
+                                            it, rd, crot, cpos, piv, sw, stol, _ptr(Rs[a:b]), _ptr(ts[a:b]), _ptr(registered[a:b]), _ptr(factor[a:b]),
+                                            _ptr(rfactor[a:b]), _ptr(info[a:b]), ws, ws_bytes, stream)
+    name, run, size = "xfh_average_poses", call, lib.xfh_pose_graph_workspace_bytes
+    if ratio is not None:
+        name, run, size = "xfh_average_poses_ratios", call_ratios, lib.xfh_pose_graph_ratios_workspace_bytes
     for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
-        _twoview.run_chunked("xfh_average_poses", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_pose_graph_workspace_bytes(n, P, V), dev,
+        _twoview.run_chunked(name, b - a, WORKSPACE_LIMIT, lambda n: size(n, P, V), dev, lambda c, d, ws, nb, st, a=a: run(a + c, a + d, ws, nb, st))
+    return out
+
+
+def baseline_ratios_batch(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weight, Ks, n_views=None, max_reproj_error=4.0, min_parallax_deg=1.0,
+                          max_depth=float('inf'), min_common=8):
+    """The ratios of the baselines of the edge pairs that share a view, from the tracks: what ties the scales of a chain's relative poses.
+
+    kpts (S,V,K,2) float32; tracks (S,T,V), track_of (S,V,K) int32 as ``build_tracks_graph`` returns them; view_pairs (S,P,2) or (P,2) int32,
+    R_rel (S,P,3,3), t_rel (S,P,3), weight (S,P) as for ``average_poses_batch`` (P <= 512, K <= 4096); Ks (S,V,3,3); n_views (S,) int32 or
+    None = V; the gates of ``triangulate_views_batch``.  A wedge is a pair of edges p < q, both valid and with a direction, whose view sets
+    share exactly one view v.  Every track with a key-point in v and in the other view of either edge is triangulated under both edges; where
+    both are valid the quotient of its two depths in v is a value, and the wedge's ratio |baseline p| / |baseline q| is the lower median
+    of its n values when n >= min_common.  A selection, no average: two calls give the same bytes whatever the order of the rows.
+    Returns a dict of CUDA tensors, all fully written: 'ratio' (S,P,P) float64 (NaN: none), 'count' (S,P,P) int32 (n; 0: no wedge),
+    'shared_view' (S,P,P) int32 (-1: no wedge), 'info' (S,8) int32 (PS_INFO_FIELDS); entries with p >= q are (NaN, 0, -1), and so is every
+    entry when there is no edge, no key-point row or no track row (written without a library call, info 0).  Asynchronous."""
+    who = "baseline_ratios_batch"
+    thr, cos_min, depth, _ = _gates(who, max_reproj_error, min_parallax_deg, max_depth, 2)
+    for t in (kpts, tracks, track_of):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f'{who}: tensors expected')
+    if kpts.dim() != 4 or kpts.shape[3] != 2:
+        raise RuntimeError('expected kpts (S,V,K,2)')
+    S, V, K = kpts.shape[:3]
+    _views(who, V)
+    if tracks.dim() != 3 or tracks.shape[0] != S or tracks.shape[2] != V or track_of.shape != (S, V, K):
+        raise RuntimeError('expected tracks (S,T,V) and track_of (S,V,K) for kpts (S,V,K,2)')
+    T = tracks.shape[1]
+    view_pairs, R_rel, t_rel, weight = torch.as_tensor(view_pairs), torch.as_tensor(R_rel), torch.as_tensor(t_rel), torch.as_tensor(weight)
+    if R_rel.dim() != 4 or R_rel.shape[0] != S or R_rel.shape[2:] != (3, 3):
+        raise RuntimeError('expected R_rel (S,P,3,3)')
+    P = R_rel.shape[1]
+    if t_rel.shape != (S, P, 3) or weight.shape != (S, P):
+        raise RuntimeError('expected t_rel (S,P,3) and weight (S,P)')
+    if view_pairs.shape not in ((S, P, 2), (P, 2)):
+        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    if P > MAX_RATIO_PAIRS:
+        raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_RATIO_PAIRS}")
+    if K > MAX_RATIO_KPTS:
+        raise _lib.XFeatHipError(f"{who}: {K} key-points per view, more than {MAX_RATIO_KPTS}")
+    if int(min_common) < 1:
+        raise _lib.XFeatHipError(f"{who}: min_common {min_common} below 1")
+    dev = kpts.device
+    for t, dt, name in ((kpts, torch.float32, 'kpts'), (tracks, torch.int32, 'tracks'), (track_of, torch.int32, 'track_of')):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f'{who}: {name} must be a contiguous {dt} tensor on the device of kpts')
+    if n_views is not None:
+        n_views = torch.as_tensor(n_views)
+        if n_views.shape != (S,):
+            raise RuntimeError('n_views must have one entry per scene')
+        n_views = n_views.to(dev).to(torch.int32).contiguous()
+    Ks = _f64(Ks, (S, V, 3, 3), dev, 'Ks')
+    if view_pairs.dim() == 2:
+        view_pairs = view_pairs.expand(S, P, 2)
+    view_pairs = view_pairs.to(dev).to(torch.int32).contiguous()
+    R_rel, t_rel, weight = (x.to(dev).to(torch.float64).contiguous() for x in (R_rel, t_rel, weight))
+    ratio = torch.empty((S, P, P), dtype=torch.float64, device=dev)
+    count = torch.empty((S, P, P), dtype=torch.int32, device=dev)
+    shared = torch.empty((S, P, P), dtype=torch.int32, device=dev)
+    info = torch.empty((S, 8), dtype=torch.int32, device=dev)
+    out = {'ratio': ratio, 'count': count, 'shared_view': shared, 'info': info}
+    if S == 0 or P == 0 or K == 0 or T == 0:  # no edge or no track: no candidate is examined, every entry is (NaN, 0, -1), info 0
+        ratio.fill_(float('nan')); count.zero_(); shared.fill_(-1); info.zero_()
+        return out
+    if not kpts.is_cuda:
+        raise _lib.XFeatHipError(f"{who} works on device-resident key-points and tracks")
+    lib = _lib.load()
+
+    def call(a, b, ws, ws_bytes, stream):
+        return lib.xfh_baseline_ratios(_ptr(kpts[a:b]), _ptr(tracks[a:b]), _ptr(track_of[a:b]), _ptr(view_pairs[a:b]), _ptr(R_rel[a:b]), _ptr(t_rel[a:b]),
+                                       _ptr(weight[a:b]), _ptr(Ks[a:b]), _ptr(n_views[a:b]) if n_views is not None else None, b - a, P, V, K, T, thr,
+                                       cos_min, depth, int(min_common), _ptr(ratio[a:b]), _ptr(count[a:b]), _ptr(shared[a:b]), _ptr(info[a:b]), ws,
+                                       ws_bytes, stream)
+    for a, b in _chunks(S):
+        _twoview.run_chunked("xfh_baseline_ratios", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_baseline_ratios_workspace_bytes(n, P, V, K), dev,
                              lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
     return out
 
@@ -520,9 +628,13 @@ def relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, 
 
 def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks, min_inliers=15, ransac=None, iterations=30, redescend=10,
                               rot_scale_deg=2.0, pos_scale_deg=2.0, min_pivot_ratio=MIN_PIVOT_RATIO, max_reproj_error=4.0, min_parallax_deg=1.0,
-                              max_depth=float('inf'), min_views=2, min_length=2, max_tracks=None, fixed_views=1, max_iterations=10, huber_px=1.0):
+                              max_depth=float('inf'), min_views=2, min_length=2, max_tracks=None, fixed_views=1, max_iterations=10, huber_px=1.0,
+                              track_scales=False, min_common=8, scale_weight=1.0, scale_tol=SCALE_TOL):
     """From the matches of an unordered set of images to a map: ``relative_poses_graph_matches`` -> ``average_poses_batch`` ->
     ``triangulate_graph_matches`` -> ``bundle_adjust_batch`` -> ``triangulate_views_batch(anchor='first')`` under the refined poses.
+    track_scales=True builds the tracks first and gives the pose graph the baseline ratios of ``baseline_ratios_batch`` (P <= 512,
+    K <= 4096): the way to positions for a sequence's pairs (v, v + 1), whose relative poses alone leave every baseline's length open
+    (pose-graph status 2, an empty map).  The result then has 'ratio', 'ratio_count', 'ratio_factor' and 'ratio_info' added.
 
     kpts (S,V,K,2), view_pairs (S,P,2) or (P,2), idx_a / idx_b (S,P,cap), n_matches (S,P) CUDA tensors; n_views (S,) int32 or None = all V;
     Ks (S,V,3,3); ransac: a dict of the relative-pose settings; the other keywords are those of the stages.
@@ -537,11 +649,22 @@ def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views
     _ba_settings(who, fixed_views, max_iterations, huber_px)
     rel = relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, min_inliers, **(ransac or {}))
     V = kpts.shape[1]
-    pg = average_poses_batch(view_pairs, rel['R_rel'], rel['t_rel'], rel['weight'], V if n_views is None else torch.as_tensor(n_views), iterations,
-                             redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio, V=V)
     vp = view_pairs.to(kpts.device).to(torch.int32).contiguous()
-    first = triangulate_graph_matches(kpts, vp, idx_a, idx_b, n_matches, n_views, Ks, pg['Rs'], pg['ts'], max_reproj_error, min_parallax_deg, max_depth,
-                                      min_views, min_length, max_tracks)
+    if track_scales:
+        tracks, track_of, n_tracks, track_info = build_tracks_graph(vp, idx_a, idx_b, n_matches, V, kpts.shape[2], min_length, max_tracks)
+        br = baseline_ratios_batch(kpts.float().contiguous(), tracks, track_of, vp, rel['R_rel'], rel['t_rel'], rel['weight'], Ks, n_views, max_reproj_error,
+                                   min_parallax_deg, max_depth, min_common)
+        pg = average_poses_batch(view_pairs, rel['R_rel'], rel['t_rel'], rel['weight'], V if n_views is None else torch.as_tensor(n_views), iterations,
+                                 redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio, V=V, ratio=br['ratio'], ratio_count=br['count'],
+                                 scale_weight=scale_weight, scale_tol=scale_tol)
+        first = triangulate_views_batch(kpts, tracks, n_views, Ks, pg['Rs'], pg['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views,
+                                        anchor='first')
+        first.update(tracks=tracks, track_of=track_of, n_tracks=n_tracks, track_info=track_info)
+    else:
+        pg = average_poses_batch(view_pairs, rel['R_rel'], rel['t_rel'], rel['weight'], V if n_views is None else torch.as_tensor(n_views), iterations,
+                                 redescend, rot_scale_deg, pos_scale_deg, min_pivot_ratio, V=V)
+        first = triangulate_graph_matches(kpts, vp, idx_a, idx_b, n_matches, n_views, Ks, pg['Rs'], pg['ts'], max_reproj_error, min_parallax_deg, max_depth,
+                                          min_views, min_length, max_tracks)
     ba = bundle_adjust_batch(kpts, first['tracks'], first['inlier_views'], first['points3d'], n_views, Ks, pg['Rs'], pg['ts'], fixed_views,
                              max_iterations, huber_px)
     out = triangulate_views_batch(kpts, first['tracks'], n_views, Ks, ba['Rs'], ba['ts'], max_reproj_error, min_parallax_deg, max_depth, min_views,
@@ -550,4 +673,6 @@ def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views
                tracks=first['tracks'], track_of=first['track_of'], n_tracks=first['n_tracks'], track_info=first['track_info'],
                Rs_init=pg['Rs'], ts_init=pg['ts'], registered=pg['registered'], edge_factor=pg['edge_factor'], pg_info=pg['info'],
                R_rel=rel['R_rel'], t_rel=rel['t_rel'], weight=rel['weight'], rel_info=rel['info'])
+    if track_scales:
+        out.update(ratio=br['ratio'], ratio_count=br['count'], ratio_factor=pg['ratio_factor'], ratio_info=br['info'])
     return out

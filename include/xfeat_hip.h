@@ -612,6 +612,41 @@ int xfh_average_poses(const int32_t* view_pairs, const double* R_rel, const doub
                       double* edge_factor, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline scales from shared tracks (DESIGN.md 3.20 / csrc/posescale_body.hpp): what gives a chain of pairs (v, v + 1) positions.
+ * Asynchronous; no host synchronisation inside; two calls give the same bits.  Every argument check returns before any launch.
+ *   xfh_baseline_ratios: kpts (S,V,K,2) fp32; tracks (S,T,V), track_of (S,V,K) int32 as xfh_build_tracks_graph writes them;
+ *     view_pairs, R_rel, t_rel, weight, n_views as for xfh_average_poses; Ks (S,V,3,3) fp64; the gates max_reproj_error (pixels),
+ *     cos_min (the cosine of the smallest parallax) and max_depth of xfh_triangulate; P <= 512, K <= 4096.  A wedge is a pair of
+ *     edges p < q, both valid and with a direction, whose view sets share exactly one view v.  Every track with a key-point in v
+ *     and in the other view of either edge is triangulated under both edges; where both are valid the quotient of its two depths
+ *     in v is a value, and the wedge's ratio |baseline p| / |baseline q| is the lower median (element (n - 1) / 2 in ascending
+ *     order) of its n values when n >= min_common.
+ *     Outputs, all (S,P,P) and fully written: ratio fp64 (NaN: none), count int32 (n, 0: no wedge), shared_view int32 (-1: no
+ *     wedge); entries with p >= q are (NaN, 0, -1).  info (S,8) int32: wedges, wedges with a ratio, tracks examined, tracks
+ *     valid, status (XFH_PS_*), 0, 0, 0.  workspace: xfh_baseline_ratios_workspace_bytes(S, P, V, K) bytes (0: bad shape).
+ *   xfh_average_poses_ratios: xfh_average_poses with the ratios in its position rounds (P <= 512): a wedge whose two edges are
+ *     both in the registered component, with a finite ratio > 0 and ratio_count > 0, adds (scale_weight ratio_count factor) h h'
+ *     to the position system, h the gradient of u_p / sqrt(r) - sqrt(r) u_q, u the baseline projected on its direction; the
+ *     factor is 1 in the first round and then Huber's or Cauchy's (as the edges') of |u_p - r u_q| / (u_p + r u_q) at scale_tol
+ *     in (0, 1].  ratio_factor (S,P,P) fp64: the final factors, 0 for a wedge that took no part.  Everything else as
+ *     xfh_average_poses.  workspace: xfh_pose_graph_ratios_workspace_bytes(S, P, V) bytes, 256-byte aligned (0: bad shape).
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_PS_OK 0
+size_t xfh_baseline_ratios_workspace_bytes(int S, int P, int V, int K);
+int xfh_baseline_ratios(const float* kpts, const int32_t* tracks, const int32_t* track_of, const int32_t* view_pairs,
+                        const double* R_rel, const double* t_rel, const double* weight, const double* Ks, const int32_t* n_views,
+                        int S, int P, int V, int K, int T, double max_reproj_error, double cos_min, double max_depth,
+                        int min_common, double* ratio, int32_t* count, int32_t* shared_view, int32_t* info, void* workspace,
+                        size_t workspace_bytes, xfh_stream stream);
+size_t xfh_pose_graph_ratios_workspace_bytes(int S, int P, int V);
+int xfh_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, const double* t_rel, const double* weight,
+                             const int32_t* n_views, const double* ratio, const int32_t* ratio_count, int S, int P, int V,
+                             int iterations, int redescend, double rot_scale_rad, double pos_scale_sin, double min_pivot_ratio,
+                             double scale_weight, double scale_tol, double* Rs_out, double* ts_out, int32_t* registered,
+                             double* edge_factor, double* ratio_factor, int32_t* info, void* workspace, size_t workspace_bytes,
+                             xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
