@@ -12,3 +12,4 @@ from .multiview import bundle_adjust_batch, refine_views_batch  # noqa: F401
 from .multiview import build_tracks_graph, triangulate_graph_matches, view_points  # noqa: F401
 from .multiview import average_poses_batch, relative_poses_graph_matches, reconstruct_graph_matches  # noqa: F401
 from .multiview import baseline_ratios_batch  # noqa: F401
+from .localization import build_map_batch, localize_map_batch, project_map, resect_views_batch  # noqa: F401

@@ -1346,6 +1346,49 @@ int xfh_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, con
     return check_launch(who);
 }
 
+// ---- map rows for localisation (k_map.hip): every check returns before any launch
+size_t xfh_map_workspace_bytes(int S, int T, int V) {
+    if (S <= 0 || S > 65535 || T <= 0 || T > (1 << 24) || V < 1 || V > 32) return 0;
+    return xfh::map_workspace_bytes(S, T, V);
+}
+
+int xfh_build_map(const float* desc, int kpt_cap, const int32_t* tracks, const float* points3d, const uint8_t* status, const int32_t* inlier_views, int S,
+                  int T, int V, int min_views, int max_points, float* points, float* map_desc, uint16_t* map_desc_f16, int32_t* track, uint8_t* n_obs,
+                  float* coherence, int32_t* n_points, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream) {
+    const char* who = "xfh_build_map";
+    if (!desc || !tracks || !points3d || !status || !inlier_views || !points || !map_desc || !map_desc_f16 || !track || !n_obs || !coherence || !n_points ||
+        !info)
+        return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 1) return fail(XFH_ERR_ARG, "%s: V %d below 1", who, V);
+    if (V > 32) return fail(XFH_ERR_UNSUPPORTED, "%s: V %d above 32", who, V);
+    if (T < 1 || T > (1 << 24) || kpt_cap < 1 || kpt_cap > (1 << 24)) return fail(XFH_ERR_ARG, "%s: bad shape (T %d, key-point capacity %d)", who, T, kpt_cap);
+    if (min_views < 1 || min_views > 32) return fail(XFH_ERR_ARG, "%s: min_views %d outside [1, 32]", who, min_views);
+    if (max_points < 1 || max_points > (1 << 24)) return fail(XFH_ERR_ARG, "%s: max_points %d outside [1, 2^24]", who, max_points);
+    if ((((uintptr_t)desc | (uintptr_t)map_desc) & 15) != 0 || ((uintptr_t)map_desc_f16 & 7) != 0)
+        return fail(XFH_ERR_ARG, "%s: the descriptor tables must be 16-byte aligned (fp16: 8)", who);
+    int rc = check_ws(workspace, workspace_bytes, xfh::map_workspace_bytes(S, T, V));
+    if (rc) return rc;
+    if (launch_build_map(desc, kpt_cap, tracks, points3d, status, inlier_views, S, T, V, min_views, max_points, points, map_desc, map_desc_f16, track, n_obs,
+                         coherence, n_points, info, workspace, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: S x T = %d x %d is more than one launch holds", who, S, T);
+    return check_launch(who);
+}
+
+int xfh_map_project(const float* points, const int32_t* n_points, int Q, int M, const double* R, const double* t, const double* K, double width,
+                    double height, double margin, float* uv, xfh_stream stream) {
+    const char* who = "xfh_map_project";
+    if (!points || !R || !t || !K || !uv) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (Q < 1 || Q > (1 << 20) || M < 1 || M > (1 << 24)) return fail(XFH_ERR_ARG, "%s: bad shape (Q %d, M %d)", who, Q, M);
+    if (!(width >= 0.0) || !(height >= 0.0) || !std::isfinite(width) || !std::isfinite(height) || (width > 0.0) != (height > 0.0))
+        return fail(XFH_ERR_ARG, "%s: image size %g x %g (both positive and finite, or both 0: none)", who, width, height);
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(XFH_ERR_ARG, "%s: margin %g must be finite and not negative", who, margin);
+    if (((uintptr_t)uv & 7) != 0) return fail(XFH_ERR_ARG, "%s: uv must be 8-byte aligned", who);
+    if (launch_map_project(points, n_points, Q, M, R, t, K, width, height, margin, uv, (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: Q x M = %d x %d is more than one launch holds", who, Q, M);
+    return check_launch(who);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

@@ -165,6 +165,13 @@ size_t track_graph_workspace_bytes(int S, int V, int K);
 int launch_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap, int V,
                               int K, int min_length, int max_tracks, int32_t* tracks, int32_t* track_of, int32_t* n_tracks, int32_t* info, void* ws,
                               hipStream_t st);
+// ---- k_map.hip (map rows for localisation: a point and a mean descriptor per usable track; the pixels of the rows under a pose) ----
+size_t map_workspace_bytes(int S, int T, int V);
+int launch_build_map(const float* desc, int kcap, const int32_t* tracks, const float* points3d, const unsigned char* status, const int32_t* inlier_views,
+                     int S, int T, int V, int min_views, int M, float* points, float* out_desc, unsigned short* desc_f16, int32_t* track,
+                     unsigned char* n_obs, float* coherence, int32_t* n_points, int32_t* info, void* ws, hipStream_t st);
+int launch_map_project(const float* points, const int32_t* n_points, int Q, int M, const double* R, const double* t, const double* K, double width,
+                       double height, double margin, float* uv, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

@@ -647,6 +647,38 @@ int xfh_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, con
                              xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Map rows for localisation (DESIGN.md 3.21 / csrc/k_map.hip): a 3D point with a descriptor for every usable track of a
+ * triangulation, to be matched against a query image as side 2 of xfh_match_mnn, and the pixels of the rows under a pose as the
+ * key-points of xfh_match_mnn_guided.  Asynchronous; no host synchronisation inside; two calls give the same bytes.  Every
+ * argument check returns before any launch.
+ *   xfh_build_map: desc (S,V,kpt_cap,64) fp32, the L2-normalised descriptor tables of the views (16-byte aligned); tracks
+ *     (S,T,V) int32, points3d (S,T,3) fp32, status (S,T) uint8, inlier_views (S,T) int32 as xfh_triangulate_views /
+ *     xfh_triangulate_tracks write them.  V <= 32 (XFH_ERR_UNSUPPORTED beyond), min_views in [1, 32], max_points = M >= 1.
+ *     View v contributes to track t iff bit v of inlier_views[t] is set (read as unsigned), 0 <= tracks[t,v] < kpt_cap and all 64
+ *     components of that row are finite.  A track is selected unless, tested in this order: status != 0; a coordinate of its point
+ *     is not finite; fewer than min_views contributing views; the sum of the contributing rows (per component, fp32, views
+ *     ascending) has a squared norm n2 that is not finite or below FLT_MIN.  The selected tracks fill the rows 0, 1, ... in
+ *     ascending track id; those beyond M are dropped and counted.
+ *     Outputs: points (S,M,3) fp32 (the input's bits), map_desc (S,M,64) fp32 = sum * (1 / sqrt(n2)), map_desc_f16 (S,M,64) the
+ *     fp16 round-to-nearest-even of 256 * map_desc (d2_f16 of xfh_match_mnn), track (S,M) int32 the track id, n_obs (S,M) uint8 the
+ *     contributing views, coherence (S,M) fp32 = sqrt(n2) / n_obs (1: all observations agree, 0: they cancel), n_points (S,) int32.
+ *     Rows from n_points on: NaN point, zero descriptors, track -1, n_obs 0, coherence 0.  info (S,8) int32: T, rows written,
+ *     skipped by status, by the point, by the views, by the norm, dropped over capacity, 0.
+ *     workspace: xfh_map_workspace_bytes(S, T, V) bytes, 256-byte aligned (0: bad shape).
+ *   xfh_map_project: points (Q,M,3) fp32, n_points (Q,) int32 or NULL = M, R (Q,3,3), t (Q,3), K (Q,3,3) fp64 row-major (device).
+ *     uv (Q,M,2) fp32 = K (R X + t) in fp64, dehomogenised and rounded once; NaN for a row >= n_points, a depth that is not finite
+ *     or not > 0, a pixel that is not finite and, when an image size is given (width, height > 0; 0, 0: none), a pixel more than
+ *     margin outside [0, width] x [0, height].
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_map_workspace_bytes(int S, int T, int V);
+int xfh_build_map(const float* desc, int kpt_cap, const int32_t* tracks, const float* points3d, const uint8_t* status,
+                  const int32_t* inlier_views, int S, int T, int V, int min_views, int max_points, float* points, float* map_desc,
+                  uint16_t* map_desc_f16, int32_t* track, uint8_t* n_obs, float* coherence, int32_t* n_points, int32_t* info,
+                  void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_map_project(const float* points, const int32_t* n_points, int Q, int M, const double* R, const double* t, const double* K,
+                    double width, double height, double margin, float* uv, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
