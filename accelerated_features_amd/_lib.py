@@ -92,6 +92,8 @@ SIGNATURES = {
     "xfh_map_workspace_bytes": (_sz, [_i, _i, _i]),
     "xfh_build_map": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "xfh_map_project": (_i, [_p, _p, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "xfh_filter_matches": (_i, [_p, _p, _p, _p, _p, C.c_int64, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "xfh_verify_matches": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, C.c_double, _p, _p, _p, _p]),
     "xfh_fundamental_workspace_bytes": (_sz, [_i, _i]),
     "xfh_find_fundamental": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "xfh_find_fundamental_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz,

@@ -1389,6 +1389,58 @@ int xfh_map_project(const float* points, const int32_t* n_points, int Q, int M, 
     return check_launch(who);
 }
 
+// ---- verification of match lists (k_matchfilter.hip, k_triangulate.hip): every check returns before any launch
+// true: the byte ranges [p, p + np) and [q, q + nq) share a byte
+static bool ranges_overlap(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && np && nq && a < b + nq && b < a + np;
+}
+
+int xfh_filter_matches(const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, const uint8_t* mask, const uint8_t* keep, int64_t L, int cap,
+                       int min_keep, int64_t* out_a, int64_t* out_b, int32_t* src, int32_t* n_out, int32_t* info, xfh_stream stream) {
+    const char* who = "xfh_filter_matches";
+    if (L < 0 || cap < 0) return fail(XFH_ERR_ARG, "%s: bad shape (L %lld, cap %d)", who, (long long)L, cap);
+    if (cap > (1 << 24)) return fail(XFH_ERR_ARG, "%s: cap %d above 2^24", who, cap);
+    if (min_keep < 0) return fail(XFH_ERR_ARG, "%s: min_keep %d is negative", who, min_keep);
+    if (L > 0x7fffffffll) return fail(XFH_ERR_UNSUPPORTED, "%s: %lld lists are more than one launch holds", who, (long long)L);
+    if (L == 0 || cap == 0) return XFH_OK;                  // nothing to read, nothing to write
+    if (!idx_a || !idx_b || !n_matches || !mask || !out_a || !out_b || !src || !n_out || !info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    const size_t n = (size_t)L, m = n * (size_t)cap;
+    const void* in[5] = {idx_a, idx_b, n_matches, mask, keep};
+    const size_t in_bytes[5] = {m * 8, m * 8, n * 4, m, n};
+    const void* out[5] = {out_a, out_b, src, n_out, info};
+    const size_t out_bytes[5] = {m * 8, m * 8, m * 4, n * 4, n * 16};
+    for (int o = 0; o < 5; ++o) {
+        for (int i = 0; i < 5; ++i)
+            if (ranges_overlap(out[o], out_bytes[o], in[i], in_bytes[i]))
+                return fail(XFH_ERR_ARG, "%s: output %d overlaps input %d (the call is not in-place)", who, o, i);
+        for (int q = 0; q < o; ++q)
+            if (ranges_overlap(out[o], out_bytes[o], out[q], out_bytes[q])) return fail(XFH_ERR_ARG, "%s: outputs %d and %d overlap", who, q, o);
+    }
+    if (launch_filter_matches(idx_a, idx_b, n_matches, mask, keep, (long long)L, cap, min_keep, out_a, out_b, src, n_out, info, (hipStream_t)stream))
+        return fail(XFH_ERR_HIP, "%s: the launch failed", who);
+    return check_launch(who);
+}
+
+int xfh_verify_matches(const float* kpts, const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches,
+                       const int32_t* n_views, int S, int P, int cap, int V, int K, const double* Ks, const double* Rs, const double* ts,
+                       double max_epipolar_error, uint8_t* mask, float* err, int32_t* pair_info, xfh_stream stream) {
+    const char* who = "xfh_verify_matches";
+    if (!kpts || !view_pairs || !idx_a || !idx_b || !n_matches || !Ks || !Rs || !ts || !mask || !pair_info) return fail(XFH_ERR_ARG, "%s: NULL argument", who);
+    if (S < 1 || S > 65535) return fail(XFH_ERR_ARG, "%s: S %d outside [1, 65535]", who, S);
+    if (V < 2) return fail(XFH_ERR_ARG, "%s: V %d below 2", who, V);
+    if (V > 32) return fail(XFH_ERR_UNSUPPORTED, "%s: V %d above 32", who, V);
+    if (P < 1 || P > 65535 || cap < 1 || cap > (1 << 24) || K < 1 || K > (1 << 24))
+        return fail(XFH_ERR_ARG, "%s: bad shape (P %d, cap %d, K %d)", who, P, cap, K);
+    if (!(max_epipolar_error > 0.0) || !std::isfinite(max_epipolar_error))
+        return fail(XFH_ERR_ARG, "%s: max_epipolar_error %g must be positive and finite", who, max_epipolar_error);
+    if (((uintptr_t)kpts & 7) != 0) return fail(XFH_ERR_ARG, "%s: kpts must be 8-byte aligned", who);
+    if (launch_verify_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, S, P, cap, V, K, Ks, Rs, ts, max_epipolar_error, mask, err, pair_info,
+                              (hipStream_t)stream))
+        return fail(XFH_ERR_UNSUPPORTED, "%s: S x P = %d x %d pairs are more than one launch holds", who, S, P);
+    return check_launch(who);
+}
+
 size_t xfh_fundamental_workspace_bytes(int P, int max_iters) {
     if (P <= 0 || max_iters <= 0) return 0;
     return xfh::fundamental_workspace_bytes(P, max_iters);

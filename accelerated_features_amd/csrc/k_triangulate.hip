@@ -2130,4 +2130,141 @@ int launch_average_poses(const int32_t* view_pairs, const double* R_rel, const d
 // the baseline ratios of the edge pairs that share a view and their terms in the position rounds
 #include "posescale_body.hpp"
 
+// ================================================================================================================================================
+// Geometric verification of match lists under world poses (tests/verification_reference.py restates it operation for operation
+// and tests/test_verification_emulated.py compiles the slice below, behind the solver and views-solver slices above, on the host): the
+// epipolar test that relpose_select_kernel (k_relpose.hip) applies under its own estimate, for the pairs of a pair graph under the poses of
+// the views -- for a pair whose own RANSAC failed but whose views are registered, and for a new selection under adjusted poses.
+// Per pair p = (a, b) of scene s, once per workgroup:
+//   * status 1: a == b or a view outside [0, n_views[s]) (n_views clamped to [0, V]; NULL: V); 2: the pose of a or b is not usable
+//     (mv_stage_pose: an entry not finite, or R all zero); 3: trel == 0; they are tested in this order;
+//   * Rrel = R_b R_a', trel = t_b - Rrel t_a, E = [trel]x Rrel (mv_pair); f = 0.5 ((fx_a + fy_a) 0.5 + (fx_b + fy_b) 0.5);
+//     thr = max_epipolar_error / f, thr2 = thr thr (RpPair::thr2_of of k_relpose.hip).
+// Per match i < n = n_matches[s, p] clamped to [0, cap], when the status is 0: it is EVALUATED when both rows are in [0, K) and the four
+//   pixel coordinates are finite; then x = ((u - cx) / fx, (v - cy) / fy) per view in fp64 (RpPair::get), r2 = tv::sampson(E, x_a, x_b),
+//   mask = r2 is finite and r2 < thr2, err = fp32 of sqrt(r2) f.  Every other entry of the (cap) row: mask 0, err NaN.
+// pair_info: the status, n, the entries with mask 1, 0.  No cheirality test: the triangulation has its gates.
+// Launch: verify_matches_kernel, one workgroup of 256 per pair (grid S P), thread 0 stages the pair in LDS, every thread walks the row in
+// steps of 256; the kept entries are counted by wave ballots into four LDS words that only their own wave's first lane writes.
+
+// ---- match verify begin (host-compilable with tests/emu/emu.hpp, behind the slices above) ----
+namespace vm {
+constexpr int ST_OK = 0, ST_PAIR = 1, ST_POSE = 2, ST_BASELINE = 3;       // pair_info word 0
+constexpr int ESS = 0, CAL = 9, THR2 = 17, FOCAL = 18, L_END = 19;          // the staged pair: E, (fx, fy, cx, cy) of a and of b, thr2, f
+constexpr unsigned NAN_BITS = 0x7fc00000u;
+}  // namespace vm
+
+struct VmArgs {
+    const float* kpts;           // (S, V, K, 2)
+    const int32_t* view_pairs;   // (S, P, 2)
+    const int64_t* idx_a;        // (S, P, cap)
+    const int64_t* idx_b;
+    const int32_t* n_matches;    // (S, P)
+    const int32_t* n_views;      // (S,) or null
+    const double* Ks;            // (S, V, 9)
+    const double* Rs;            // (S, V, 9)
+    const double* ts;            // (S, V, 3)
+    int P, cap, V, K;
+    double max_err;
+    unsigned char* mask;         // (S, P, cap)
+    float* err;                  // (S, P, cap) or null
+    int32_t* info;               // (S, P, 4)
+};
+
+__device__ inline bool vm_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// the pair (a, b) of a scene with nv views: its status and, when that is 0, the vm::L_END doubles of o
+__device__ inline int vm_stage_pair(int a, int b, int nv, const double* Ks, const double* Rs, const double* ts, double max_err, double* o) {
+    if (a == b || (unsigned)a >= (unsigned)nv || (unsigned)b >= (unsigned)nv) return vm::ST_PAIR;
+    double pa[mv::RREL], pb[mv::RREL];                     // (what mv_stage_pose writes: ROT, TRA, CAL, CEN, OK)
+    mv_stage_pose(Rs + (size_t)a * 9, ts + (size_t)a * 3, Ks + (size_t)a * 9, pa);
+    mv_stage_pose(Rs + (size_t)b * 9, ts + (size_t)b * 3, Ks + (size_t)b * 9, pb);
+    if (pa[mv::OK] == 0.0 || pb[mv::OK] == 0.0) return vm::ST_POSE;
+    double Rrel[9], trel[3];
+    mv_pair(pa + mv::ROT, pa + mv::TRA, pb + mv::ROT, pb + mv::TRA, Rrel, trel, o + vm::ESS);
+    if (trel[0] == 0.0 && trel[1] == 0.0 && trel[2] == 0.0) return vm::ST_BASELINE;
+    // CAL of a staged pose is (fx, fy, cx, cy)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { o[vm::CAL + k] = pa[mv::CAL + k]; o[vm::CAL + 4 + k] = pb[mv::CAL + k]; }
+    const double f = 0.5 * ((o[vm::CAL] + o[vm::CAL + 1]) * 0.5 + (o[vm::CAL + 4] + o[vm::CAL + 5]) * 0.5);
+    const double thr = max_err / f;
+    o[vm::THR2] = thr * thr;
+    o[vm::FOCAL] = f;
+    return vm::ST_OK;
+}
+
+__global__ __launch_bounds__(256) void verify_matches_kernel(VmArgs a) {
+    __shared__ double pr[vm::L_END];
+    __shared__ int st_sh;
+    __shared__ int wave_n[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t pair = blockIdx.x, s = pair / (size_t)a.P;
+    if (tid == 0) {
+        int nv = a.n_views ? a.n_views[s] : a.V;
+        nv = nv < 0 ? 0 : (nv > a.V ? a.V : nv);
+        const size_t v0 = s * (size_t)a.V;
+        st_sh = vm_stage_pair(a.view_pairs[2 * pair], a.view_pairs[2 * pair + 1], nv, a.Ks + v0 * 9, a.Rs + v0 * 9, a.ts + v0 * 3, a.max_err, pr);
+    }
+    __syncthreads();
+    const int st = st_sh;
+    int n = a.n_matches[pair];
+    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    const int live = st == vm::ST_OK ? n : 0;
+    double E[9], cal[8];                                    // (LDS broadcasts; a pair that is not ok left pr unwritten)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = live > 0 ? pr[vm::ESS + k] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cal[k] = live > 0 ? pr[vm::CAL + k] : 0.0;
+    const double thr2 = live > 0 ? pr[vm::THR2] : 0.0, f = live > 0 ? pr[vm::FOCAL] : 0.0;
+    // views in range: vm_stage_pair checked them for a live pair
+    const int va = live > 0 ? a.view_pairs[2 * pair] : 0, vb = live > 0 ? a.view_pairs[2 * pair + 1] : 0;
+    const float* ka = a.kpts + (s * (size_t)a.V + va) * a.K * 2;
+    const float* kb = a.kpts + (s * (size_t)a.V + vb) * a.K * 2;
+    const size_t base = pair * (size_t)a.cap;
+    const float nanv = __uint_as_float(vm::NAN_BITS);
+    int kept = 0;
+    for (int b0 = 0; b0 < a.cap; b0 += 256) {               // (the trip count is the same for every thread: the ballot is the whole wave's)
+        const int i = b0 + tid;
+        bool in = false;
+        float e = nanv;
+        if (i < live) {
+            const unsigned long long ra = (unsigned long long)a.idx_a[base + i], rb = (unsigned long long)a.idx_b[base + i];      // (-1 is a huge unsigned one)
+            if (ra < (unsigned long long)a.K && rb < (unsigned long long)a.K) {
+                const float2 q0 = *reinterpret_cast<const float2*>(ka + 2 * ra);
+                const float2 q1 = *reinterpret_cast<const float2*>(kb + 2 * rb);
+                if (vm_finite(q0.x) && vm_finite(q0.y) && vm_finite(q1.x) && vm_finite(q1.y)) {
+                    const double r2 = tv::sampson(E, ((double)q0.x - cal[2]) / cal[0], ((double)q0.y - cal[3]) / cal[1], ((double)q1.x - cal[6]) / cal[4],
+                                                  ((double)q1.y - cal[7]) / cal[5]);
+                    in = tv::is_finite(r2) && r2 < thr2;
+                    e = (float)(sqrt(r2) * f);
+                }
+            }
+        }
+        if (i < a.cap) {
+            a.mask[base + i] = in ? 1 : 0;
+            if (a.err) a.err[base + i] = e;
+        }
+        kept += (int)__popcll(__ballot(in));                // (the same in every lane of a wave)
+    }
+    if (lane == 0) wave_n[wave] = kept;
+    __syncthreads();
+    if (tid == 0) {
+        int32_t* info = a.info + pair * 4;
+        info[0] = st; info[1] = n; info[2] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]); info[3] = 0;
+    }
+}
+// ---- match verify end ----
+
+int launch_verify_matches(const float* kpts, const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches,
+                          const int32_t* n_views, int S, int P, int cap, int V, int K, const double* Ks, const double* Rs, const double* ts,
+                          double max_epipolar_error, unsigned char* mask, float* err, int32_t* pair_info, hipStream_t st) {
+    if (S < 1 || S > 65535 || P < 1 || cap < 1 || V < 2 || V > mv::MAX_VIEWS || K < 1) return -1;
+    if ((long long)S * P > 0x7fffffffll) return -1;         // the grid is one-dimensional over the pairs
+    VmArgs a = {};
+    a.kpts = kpts; a.view_pairs = view_pairs; a.idx_a = idx_a; a.idx_b = idx_b; a.n_matches = n_matches; a.n_views = n_views; a.Ks = Ks; a.Rs = Rs; a.ts = ts;
+    a.P = P; a.cap = cap; a.V = V; a.K = K; a.max_err = max_epipolar_error; a.mask = mask; a.err = err; a.info = pair_info;
+    verify_matches_kernel<<<(unsigned)((long long)S * P), 256, 0, st>>>(a);
+    return 0;
+}
+
 }  // namespace xfh

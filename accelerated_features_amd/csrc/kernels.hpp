@@ -160,6 +160,13 @@ int launch_average_poses_ratios(const int32_t* view_pairs, const double* R_rel, 
                                 const double* ratio, const int32_t* ratio_count, int S, int P, int V, int iterations, int redescend, double rot_scale_rad,
                                 double pos_scale_sin, double min_pivot_ratio, double scale_weight, double scale_tol, double* Rs_out, double* ts_out,
                                 int32_t* registered, double* edge_factor, double* ratio_factor, int32_t* info, void* ws, hipStream_t st);
+// (geometric verification of the match lists of a pair graph under the world poses of the views: the epipolar test of every match)
+int launch_verify_matches(const float* kpts, const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches,
+                          const int32_t* n_views, int S, int P, int cap, int V, int K, const double* Ks, const double* Rs, const double* ts,
+                          double max_epipolar_error, unsigned char* mask, float* err, int32_t* pair_info, hipStream_t st);
+// ---- k_matchfilter.hip (order-preserving compaction of match lists by a mask) ----
+int launch_filter_matches(const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, const unsigned char* mask, const unsigned char* keep,
+                          long long L, int cap, int min_keep, int64_t* out_a, int64_t* out_b, int32_t* src, int32_t* n_out, int32_t* info, hipStream_t st);
 // ---- k_tracks.hip (key-point tracks over a graph of view pairs: connected components of the match graph by a lock-free union-find) ----
 size_t track_graph_workspace_bytes(int S, int V, int K);
 int launch_build_tracks_graph(const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, int S, int P, int cap, int V,

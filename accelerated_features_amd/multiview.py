@@ -629,12 +629,16 @@ def relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, 
 def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks, min_inliers=15, ransac=None, iterations=30, redescend=10,
                               rot_scale_deg=2.0, pos_scale_deg=2.0, min_pivot_ratio=MIN_PIVOT_RATIO, max_reproj_error=4.0, min_parallax_deg=1.0,
                               max_depth=float('inf'), min_views=2, min_length=2, max_tracks=None, fixed_views=1, max_iterations=10, huber_px=1.0,
-                              track_scales=False, min_common=8, scale_weight=1.0, scale_tol=SCALE_TOL):
+                              track_scales=False, min_common=8, scale_weight=1.0, scale_tol=SCALE_TOL, verified=False):
     """From the matches of an unordered set of images to a map: ``relative_poses_graph_matches`` -> ``average_poses_batch`` ->
     ``triangulate_graph_matches`` -> ``bundle_adjust_batch`` -> ``triangulate_views_batch(anchor='first')`` under the refined poses.
     track_scales=True builds the tracks first and gives the pose graph the baseline ratios of ``baseline_ratios_batch`` (P <= 512,
     K <= 4096): the way to positions for a sequence's pairs (v, v + 1), whose relative poses alone leave every baseline's length open
     (pose-graph status 2, an empty map).  The result then has 'ratio', 'ratio_count', 'ratio_factor' and 'ratio_info' added.
+    verified=True compacts the lists to each pair's RANSAC inliers right after the relative poses (``filter_matches_batch`` with
+    rel['inliers'], a pair without a pose emptied) and gives the compacted lists to every later stage: one wrong match
+    joins two tracks into a component that is dropped whole, so raw mutual-nearest-neighbour lists leave almost no track.  The result then
+    has 'idx_a_verified', 'idx_b_verified', 'n_verified', 'match_src' and 'filter_info' added.
 
     kpts (S,V,K,2), view_pairs (S,P,2) or (P,2), idx_a / idx_b (S,P,cap), n_matches (S,P) CUDA tensors; n_views (S,) int32 or None = all V;
     Ks (S,V,3,3); ransac: a dict of the relative-pose settings; the other keywords are those of the stages.
@@ -650,6 +654,9 @@ def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views
     rel = relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, min_inliers, **(ransac or {}))
     V = kpts.shape[1]
     vp = view_pairs.to(kpts.device).to(torch.int32).contiguous()
+    if verified:
+        from . import verification
+        idx_a, idx_b, n_matches, match_src, filter_info = verification.filter_matches_batch(idx_a, idx_b, n_matches, rel['inliers'], rel['weight'] > 0)
     if track_scales:
         tracks, track_of, n_tracks, track_info = build_tracks_graph(vp, idx_a, idx_b, n_matches, V, kpts.shape[2], min_length, max_tracks)
         br = baseline_ratios_batch(kpts.float().contiguous(), tracks, track_of, vp, rel['R_rel'], rel['t_rel'], rel['weight'], Ks, n_views, max_reproj_error,
@@ -675,4 +682,6 @@ def reconstruct_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, n_views
                R_rel=rel['R_rel'], t_rel=rel['t_rel'], weight=rel['weight'], rel_info=rel['info'])
     if track_scales:
         out.update(ratio=br['ratio'], ratio_count=br['count'], ratio_factor=pg['ratio_factor'], ratio_info=br['info'])
+    if verified:
+        out.update(idx_a_verified=idx_a, idx_b_verified=idx_b, n_verified=n_matches, match_src=match_src, filter_info=filter_info)
     return out

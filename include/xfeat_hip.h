@@ -679,6 +679,45 @@ int xfh_map_project(const float* points, const int32_t* n_points, int Q, int M, 
                     double width, double height, double margin, float* uv, xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Geometric verification of match lists before they become tracks (DESIGN.md 3.22 / csrc/k_matchfilter.hip, csrc/k_triangulate.hip).
+ * Asynchronous; no host synchronisation inside; no workspace; two calls give the same bytes.  Every argument check returns before
+ * any launch.
+ *   xfh_filter_matches: the order-preserving compaction of L match lists by a mask.  idx_a, idx_b (L,cap) int64, n_matches (L,)
+ *     int32 (read clamped to [0, cap]), mask (L,cap) uint8 (non-zero keeps an entry; the inlier mask of any estimator), keep (L,)
+ *     uint8 or NULL (zero empties the list), min_keep >= 0 (a list that keeps fewer entries is emptied).  Outputs: out_a, out_b
+ *     (L,cap) int64 = the kept entries in their original order, then -1; src (L,cap) int32 = the original position of each kept
+ *     entry, then -1 (to gather scores, refined coordinates or a second mask); n_out (L,) int32; info (L,4) int32: entries read,
+ *     entries whose mask is set, the reason the list was emptied (XFH_FILTER_*), 0.  L = 0 or cap = 0 return without a launch;
+ *     L above 2^31 - 1 is XFH_ERR_UNSUPPORTED.  The call is not in-place: an output range that overlaps an input range (or
+ *     another output) is XFH_ERR_ARG.
+ *   xfh_verify_matches: the epipolar test of every match of the pairs of a pair graph under the world poses of the views.
+ *     kpts (S,V,K,2) fp32 (8-byte aligned); view_pairs (S,P,2) int32, idx_a, idx_b (S,P,cap) int64, n_matches (S,P) int32 as for
+ *     xfh_build_tracks_graph; n_views (S,) int32 or NULL = V; Ks (S,V,3,3), Rs (S,V,3,3), ts (S,V,3) fp64, x_v = R_v X + t_v;
+ *     max_epipolar_error in pixels, finite and > 0; V <= 32 (XFH_ERR_UNSUPPORTED beyond).  Per pair (a, b): status
+ *     XFH_VERIFY_PAIR when a == b or a view is outside [0, n_views); XFH_VERIFY_POSE when a pose has an entry that is not finite
+ *     or an all-zero R; XFH_VERIFY_BASELINE when t_rel = t_b - R_rel t_a is zero (R_rel = R_b R_a'); else E = [t_rel]x R_rel and
+ *     the threshold max_epipolar_error / f, f the mean of the four focal lengths (what xfh_estimate_relpose uses).  A match is
+ *     evaluated when the pair is ok, both rows are in [0, K) and its four pixel coordinates are finite: r2 = its Sampson error
+ *     in normalised coordinates (fp64), mask = r2 finite and r2 < threshold^2 (strict).  No cheirality test.
+ *     Outputs: mask (S,P,cap) uint8, 0 for every entry that is not evaluated; err (S,P,cap) fp32 or NULL = sqrt(r2) f in pixels,
+ *     rounded once, NaN where nothing was evaluated; pair_info (S,P,4) int32: status, entries read, entries kept, 0.
+ * ---------------------------------------------------------------------------------------- */
+#define XFH_FILTER_NONE 0
+#define XFH_FILTER_BY_KEEP 1
+#define XFH_FILTER_BY_MIN_KEEP 2
+#define XFH_VERIFY_OK 0
+#define XFH_VERIFY_PAIR 1
+#define XFH_VERIFY_POSE 2
+#define XFH_VERIFY_BASELINE 3
+int xfh_filter_matches(const int64_t* idx_a, const int64_t* idx_b, const int32_t* n_matches, const uint8_t* mask, const uint8_t* keep,
+                       int64_t L, int cap, int min_keep, int64_t* out_a, int64_t* out_b, int32_t* src, int32_t* n_out, int32_t* info,
+                       xfh_stream stream);
+int xfh_verify_matches(const float* kpts, const int32_t* view_pairs, const int64_t* idx_a, const int64_t* idx_b,
+                       const int32_t* n_matches, const int32_t* n_views, int S, int P, int cap, int V, int K, const double* Ks,
+                       const double* Rs, const double* ts, double max_epipolar_error, uint8_t* mask, float* err, int32_t* pair_info,
+                       xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
