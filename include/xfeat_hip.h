@@ -181,14 +181,17 @@ int xfh_conv_layer(xfh_handle h, int layer, const float* in, int B, int Hin, int
  *
  *   heat (B,H,W), reliab (B,H/8,W/8), feats (B,H/8,W/8,64) as produced by xfh_backbone
  *   invnorm          (B,H/8,W/8) from the same xfh_backbone call, or NULL (then computed here in one extra pass over feats)
- *   threshold        detection threshold (strict >)
+ *   threshold        detection threshold (strict >).  May be negative: a pixel outside the image never takes part in a
+ *                    window's maximum (-inf padding), whatever the sign of the values.
  *   top_k            any positive value (fewer candidates than top_k => shorter lists, like the reference)
  *   nms_capacity     capacity of the candidate list per image.  If n_candidates[b] comes back
  *                    larger, candidates were dropped in row-major order: re-run with a
  *                    capacity >= max(n_candidates) (H*W is always enough).
  *   rw, rh           original/processed size ratios (key-points are returned multiplied by them)
  * outputs (fixed capacity, entries past n_valid[b] are zero-filled):
- *   kpts (B,top_k,2) fp32 (x,y) ; scores (B,top_k) descending ; desc (B,top_k,64) unit norm
+ *   kpts (B,top_k,2) fp32 (x,y) ; scores (B,top_k) descending, EQUAL scores in candidate order (row-major: y, then x,
+ *   among the first nms_capacity candidates) ; desc (B,top_k,64) unit norm (a zero row where every feature under the
+ *   key-point's sixteen taps is zero)
  *   desc_f16 (B,top_k,64) optional (may be NULL): fp16 (round-to-nearest-even) of 256 * desc, the operand of xfh_match_mnn's filter sweep
  *   n_valid (B) int32       = number of returned points with score > 0 (they form a prefix)
  *   n_candidates (B) int32  = NMS candidates found (uncapped)
@@ -203,7 +206,8 @@ int xfh_detect_sparse(xfh_handle h, const float* heat, const float* reliab, cons
  * Semi-dense extraction.  Replaces XFeat.extractDense after the backbone
  * (modules/xfeat.py:362-375): top-k of the reliability map (descending), RAW 64-D features of
  * those cells and their corner coordinates (8*(j,i)*(rw,rh)) / scale_div (scale_div = s of
- * extract_dualscale, modules/xfeat.py:388; 1 otherwise).
+ * extract_dualscale, modules/xfeat.py:388; 1 otherwise).  Cells of EQUAL reliability come out lower cell index
+ * (i*w + j) first.  (Both tie rules hold for values without NaN; -0.0 and +0.0 are not promised to tie.)
  *   kpts (B,k,2), desc (B,k,64), cell_index (B,k) int32 (may be NULL); k <= h*w
  * ---------------------------------------------------------------------------------------- */
 size_t xfh_dense_workspace_bytes(int B, int h, int w, int k);
@@ -299,7 +303,8 @@ int xfh_refine_matches(xfh_handle h, const float* desc0, const float* desc1, con
  *   xfh_nms          : XFeat.NMS (modules/xfeat.py:249-263), any odd kernel_size (the reference's generic
  *                      max_pool2d(k, 1, k/2) window; 5 is what the hot path uses and has the tiled kernel).
  *                      xy (B,capacity,2) int64 (x,y) in row-major order, zero padded; n_candidates (B) int32
- *                      uncapped.  workspace: xfh_detect_workspace_bytes(B,H,W,1,capacity).
+ *                      uncapped (beyond capacity the LAST candidates in row-major order are dropped).  The threshold
+ *                      may be negative: windows are clipped to the image (-inf padding) for values of any sign.  workspace: xfh_detect_workspace_bytes(B,H,W,1,capacity).
  *   xfh_sample_sparse: InterpolateSparse2d.forward (modules/interpolator.py:10-33; the XFeat.interpolator attribute,
  *                      modules/xfeat.py:37): x (B,C,Hm,Wm) NCHW, pos (B,N,2) fp32 (x,y) in an H x W frame ->
  *                      out (B,N,C); grid_sample semantics (align_corners=False, zeros padding) with the reference's

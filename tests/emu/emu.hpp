@@ -45,7 +45,8 @@ struct Workgroup {
     std::vector<std::unique_ptr<std::barrier<>>> row_bar;      // one per 16 lanes (a DPP row): for kernels whose 16-lane groups leave early as a whole (descriptor_kernel)
     std::vector<h8> opa, opb;      // [thread]
     std::vector<float> opa32, opb32;      // [thread][8]
-    Workgroup(int n, size_t lds_bytes) : nthreads(n), lds(lds_bytes + 64, 0xff), bar(n), opa(n), opb(n), opa32(8 * n), opb32(8 * n) {      // (LDS starts as NaN patterns: nothing may rely on zeros)
+    std::vector<unsigned> xch;            // [thread][8]: the slots of update_dpp (0, 1) and permlane_swap (2 .. 5), two alternating sets each
+    Workgroup(int n, size_t lds_bytes) : nthreads(n), lds(lds_bytes + 64, 0xff), bar(n), opa(n), opb(n), opa32(8 * n), opb32(8 * n), xch(8 * n) {      // (LDS starts as NaN patterns: nothing may rely on zeros)
         for (int w = 0; w < n / 64; ++w) wave_bar.emplace_back(new std::barrier<>(64));
         for (int r = 0; r < n / 16; ++r) row_bar.emplace_back(new std::barrier<>(16));
     }
@@ -112,22 +113,42 @@ inline f16v mfma32x2(float a, float b, f16v c) {
     return d;
 }
 // v_mov_b32_dpp within a ROW of 16 lanes (all that the kernels emulated here use): quad_perm (ctrl < 0x100), row_mirror (0x140), row_half_mirror (0x141), row_newbcast:n
-// (0x150 + n).  Every source lane of these is in the lane's own row and the rows' lanes reach the instruction together, so the exchange synchronises the row, not the wave --
-// a row whose 16 lanes have all returned (descriptor_kernel: rows past the list) is simply absent.  row_mask / bank_mask 0xf, bound_ctrl irrelevant (no invalid source).
-inline unsigned update_dpp(unsigned, unsigned src, int ctrl, int row_mask, int bank_mask, bool) {
+// (0x150 + n), row_shl:4 (0x104: lane l <- l + 4), row_shr:4 (0x114: lane l <- l - 4), row_ror:8 (0x128: lane l <- l ^ 8).  Every source lane of these is in the lane's own
+// row and the rows' lanes reach the instruction together, so the exchange synchronises the row, not the wave -- a row whose 16 lanes have all returned (descriptor_kernel:
+// rows past the list) is simply absent.  row_mask / bank_mask 0xf.  Only the row shifts have lanes without a source (beyond the row's end): bound_ctrl gives them 0, else `old`.
+inline thread_local unsigned dpp_turn = 0, swap_turn = 0;
+inline unsigned update_dpp(unsigned old, unsigned src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
     const int t = tidx.x, l = t & 15, base = t & ~15;
     if (row_mask != 0xf || bank_mask != 0xf) std::abort();
-    std::memcpy(&wg->opb32[t * 8], &src, 4);
+    // ONE barrier per exchange: the slots alternate, and a lane that writes slot s again has passed the barrier of the exchange in between, which every lane of the row
+    // reaches only after it has read slot s
+    const int slot = dpp_turn++ & 1;
+    wg->xch[t * 8 + slot] = src;
     wg->row_bar[t >> 4]->arrive_and_wait();
     int sl;
     if (ctrl < 0x100) sl = (l & ~3) | ((ctrl >> (2 * (l & 3))) & 3);
     else if (ctrl == 0x140) sl = 15 - l;
     else if (ctrl == 0x141) sl = (l & 8) | (7 - (l & 7));
     else if (ctrl >= 0x150 && ctrl < 0x160) sl = ctrl - 0x150;
+    else if (ctrl == 0x104) sl = l + 4;
+    else if (ctrl == 0x114) sl = l - 4;
+    else if (ctrl == 0x128) sl = (l + 8) & 15;
     else std::abort();
-    unsigned r;
-    std::memcpy(&r, &wg->opb32[(base + sl) * 8], 4);
-    wg->row_bar[t >> 4]->arrive_and_wait();
+    return (sl >= 0 && sl < 16) ? wg->xch[(base + sl) * 8 + slot] : (bound_ctrl ? 0u : old);
+}
+// v_permlane16_swap / v_permlane32_swap of (vdst, src) = (a, b): the odd rows of 16 (the upper half) of vdst trade places with the even rows (the lower half) of src;
+// -> {vdst, src} afterwards.  With a == b: r[0] = rows {0, 0, 2, 2} ({lo, lo}), r[1] = rows {1, 1, 3, 3} ({hi, hi}).  Through the wave barrier, alternating slots as above.
+typedef unsigned u2 __attribute__((ext_vector_type(2)));
+inline u2 permlane_swap(unsigned a, unsigned b, int width) {
+    const int t = tidx.x, w = t >> 6, l = t & 63;
+    const int slot = 2 + 2 * (swap_turn++ & 1);
+    wg->xch[t * 8 + slot] = a;
+    wg->xch[t * 8 + slot + 1] = b;
+    wg->wave_bar[w]->arrive_and_wait();
+    u2 r = {a, b};
+    const unsigned v = wg->xch[(w * 64 + (l ^ width)) * 8 + slot + ((l & width) ? 1 : 0)];
+    if (l & width) r[0] = v;      // an odd row of vdst <- the even row of src below it
+    else r[1] = v;                // an even row of src <- the odd row of vdst above it
     return r;
 }
 // value of lane ^ mask of the same wave
@@ -280,6 +301,8 @@ typedef void* xfh_lptr_t;
 typedef emu::Rsrc __amdgpu_buffer_rsrc_t;
 #define __builtin_amdgcn_readfirstlane(x) (x)
 #define __builtin_amdgcn_update_dpp(old, src, ctrl, rm, bm, bc) emu::update_dpp(old, src, ctrl, rm, bm, bc)
+#define __builtin_amdgcn_permlane16_swap(a, b, fi, bc) emu::permlane_swap(a, b, 16)
+#define __builtin_amdgcn_permlane32_swap(a, b, fi, bc) emu::permlane_swap(a, b, 32)
 #define __builtin_amdgcn_fmed3f(a, b, c) emu::med3(a, b, c)
 #define __builtin_amdgcn_sched_barrier(m) ((void)0)
 #define __builtin_amdgcn_perm(hi, lo, sel) emu::perm(hi, lo, sel)

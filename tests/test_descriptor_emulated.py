@@ -9,6 +9,8 @@ import tempfile
 import numpy as np
 import pytest
 
+import detect_reference as DR
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "accelerated_features_amd", "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
@@ -41,19 +43,6 @@ def emu_bin():
 def _float_ord(f):
     u = np.float32(f).view(np.uint32)
     return np.uint32(~u) if u & np.uint32(0x80000000) else np.uint32(u | np.uint32(0x80000000))
-
-
-def _sample_coord(p, S, Sm):      # the kernel's (= the reference's) fp32 operation order; the last step is one fused multiply-add
-    q = np.float32(p) / np.float32(S - 1)
-    g1 = np.float32(np.float32(np.float32(2.0) * q) - np.float32(1.0)) + np.float32(1.0)
-    return np.float32(np.float64(np.float32(g1)) * np.float64(np.float32(Sm) * np.float32(0.5)) - 0.5)
-
-
-def _cubic(t):
-    A = -0.75
-    def near(x): return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0
-    def far(x): return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A
-    return [far(t + 1.0), near(t), near(1.0 - t), far(2.0 - t)]
 
 
 @pytest.mark.parametrize("B,H,W,top_k,nsel", [(1, 64, 96, 64, [64]), (2, 96, 64, 48, [48, 21]), (1, 480, 640, 160, [150]), (9, 32, 32, 16, [16, 0, 3, 16, 7, 16, 1, 15, 16])])
@@ -94,26 +83,16 @@ def test_descriptor_kernel_on_the_host(emu_bin, B, H, W, top_k, nsel):
     kp = take(B * top_k * 2, np.float32).reshape(B, top_k, 2); sc_d = take(B * top_k, np.float32).reshape(B, top_k)
     de = take(B * top_k * 64, np.float32).reshape(B, top_k, 64); d16 = take(B * top_k * 64, np.float16).reshape(B, top_k, 64); nv = take(B, np.int32)
     assert o == len(out)
-    fn = feats.astype(np.float64) * inv.astype(np.float64)[..., None]
     worst = 0.0
     for b in range(B):
         k = nsel[b]
         assert nv[b] == int((scores[b, :k] > 0).sum())
         assert np.array_equal(sc_d[b, :k], scores[b, :k]) and not sc_d[b, k:].any() and not kp[b, k:].any() and not de[b, k:].any() and not d16[b, k:].any()
-        for j in range(k):
-            c = int(cand[b, int(skeys[b, j] & np.uint64(0xffffffff))]); x, y = c & 0xffff, c >> 16
-            assert kp[b, j, 0] == np.float32(x) * rw and kp[b, j, 1] == np.float32(y) * rh
-            ux, uy = _sample_coord(x, W, wc), _sample_coord(y, H, hc)
-            fx, fy = np.floor(ux), np.floor(uy)
-            wx, wy = _cubic(float(np.float32(ux - fx))), _cubic(float(np.float32(uy - fy)))
-            acc = np.zeros(64)
-            for r in range(4):
-                for i in range(4):
-                    yy, xx = int(fy) - 1 + r, int(fx) - 1 + i
-                    if 0 <= yy < hc and 0 <= xx < wc:
-                        acc += wy[r] * wx[i] * fn[b, yy * wc + xx]
-            ref = acc / max(np.sqrt((acc * acc).sum()), 1e-12)
-            worst = max(worst, float(np.abs(de[b, j] - ref).max()))
+        c = cand[b, (skeys[b, :k] & np.uint64(0xffffffff)).astype(np.int64)].astype(np.int64)
+        xs, ys = c & 0xffff, c >> 16
+        assert np.array_equal(kp[b, :k, 0], xs.astype(np.float32) * rw) and np.array_equal(kp[b, :k, 1], ys.astype(np.float32) * rh)
+        if k:
+            worst = max(worst, float(np.abs(de[b, :k] - DR.descriptors(feats[b], ys, xs, H, W, inv=inv[b])).max()))      # (inv is an input of the kernel: the same fp32 values)
     print(f"B {B} {H}x{W} top_k {top_k}: max |desc - float64| {worst:.3g}")
     assert worst <= 1.5e-6
     assert np.array_equal(d16, (de * np.float32(256.0)).astype(np.float16))          # the fp16 copies: RNE(256 * row) of the kernel's own fp32 rows
