@@ -1,12 +1,15 @@
-"""What the three two-view estimators (homography.py, pose.py, fundamental.py) share on the Python side: the device and argument checks
-of their two kinds of entry point ((P, cap, 2) point tensors; key-points + the matcher's index lists), the seed of a chunk of pairs and
-the loop that runs a batch in chunks of pairs under a workspace limit.  Private: the public names live in the three modules."""
+"""What the RANSAC estimators over pairs (homography.py, pose.py, fundamental.py, absolute_pose.py, alignment.py) share on the Python side:
+the device and argument checks of their two kinds of entry point (point tensors; tables + the matcher's index lists), the intrinsics
+argument, the seed of a chunk of pairs and the loop that runs a batch in chunks of pairs under the workspace limit.  structure.py and the
+scene-batched stages (_scenes.py) use the device, the pointers and that loop.  Private: the public names live in those modules."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
+
+WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs or scenes
 
 
 def device(what):
@@ -17,6 +20,21 @@ def device(what):
 
 def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def tensors(who, *ts):
+    for t in ts:
+        if not torch.is_tensor(t):
+            raise RuntimeError(f'{who}: tensors expected')
+
+
+def intrinsics(K, P, dev):
+    K = torch.as_tensor(K, dtype=torch.float64)
+    if K.shape == (3, 3):
+        K = K.expand(P, 3, 3)
+    if K.shape != (P, 3, 3):
+        raise RuntimeError('intrinsics must be (3,3) or (P,3,3)')
+    return K.to(dev).contiguous()
 
 
 def as_points(x):
@@ -128,9 +146,7 @@ def check_points_3d3d(what, pts_a, pts_b, counts):
 def check_matches_3d3d(who, points_a, points_b, idx_a, idx_b, n_matches):
     """Two point tables (P,Ka,3), (P,Kb,3) float32 (Ka and Kb independent), idx (P,cap) int64, n_matches (P,) int32, all device-resident.
     Returns (device, P, cap)."""
-    for t in (points_a, points_b, idx_a, idx_b, n_matches):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    tensors(who, points_a, points_b, idx_a, idx_b, n_matches)
     if idx_a.dim() != 2:
         raise RuntimeError('expected idx (P,cap)')
     P, cap = idx_a.shape

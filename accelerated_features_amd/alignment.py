@@ -16,12 +16,11 @@ import math
 import torch
 
 from . import _lib, _twoview
-from ._twoview import chunk_seed, ptr as _ptr           # chunk_seed is public here: chunk_seed(seed, p) = the seed of pair p alone
+from ._twoview import WORKSPACE_LIMIT, chunk_seed, ptr as _ptr      # chunk_seed is public here: chunk_seed(seed, p) = the seed of pair p alone
 from .absolute_pose import unproject_keypoints
 
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "cost_lo", "cost_hi")
 MAX_ITERATIONS = 16384                       # the kernel's limit; more is an error
-WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs
 _WHAT = "3D-3D alignment"
 
 

@@ -1,7 +1,7 @@
 // C ABI of the LighterGlue matcher (include/xfeat_hip.h, section "LighterGlue"): weight packing + the per-pair
 // schedule of kernels.  Replaces kornia.feature.lightglue.LightGlue.forward as configured by
 // modules/lighterglue.py:12-27 and called from modules/xfeat.py:131-162.
-#include "../../include/xfeat_hip.h"
+#include "api_common.hpp"
 #include "kernels.hpp"
 #include <algorithm>
 #include <cmath>
@@ -11,8 +11,6 @@
 #include <vector>
 
 using namespace xfh;
-
-int xfh_set_error(int code, const char* fmt, ...);      // api.hip
 
 namespace {
 constexpr int LG_LAYERS = 6, LG_D = 96, LG_IN = 64;
@@ -65,18 +63,18 @@ size_t xfh_lg_weight_array_floats(int i) {
 }
 
 int xfh_lg_create(const float* const* host_arrays, int n_arrays, int device, xfh_lg_handle* out) {
-    if (!host_arrays || !out) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_create: NULL argument");
+    if (!host_arrays || !out) return fail(XFH_ERR_ARG, "xfh_lg_create: NULL argument");
     std::vector<std::pair<int, int>> sh; lg_shapes(sh);
-    if (n_arrays != (int)sh.size()) return xfh_set_error(XFH_ERR_WEIGHTS, "xfh_lg_create: expected %d weight arrays, got %d", (int)sh.size(), n_arrays);
+    if (n_arrays != (int)sh.size()) return fail(XFH_ERR_WEIGHTS, "xfh_lg_create: expected %d weight arrays, got %d", (int)sh.size(), n_arrays);
     for (int i = 0; i < n_arrays; ++i)
-        if (!host_arrays[i]) return xfh_set_error(XFH_ERR_WEIGHTS, "xfh_lg_create: weight array %d is NULL", i);
+        if (!host_arrays[i]) return fail(XFH_ERR_WEIGHTS, "xfh_lg_create: weight array %d is NULL", i);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return xfh_set_error(XFH_ERR_DEVICE, "xfh_lg_create: no HIP device visible");
-    if (device < 0 || device >= ndev) return xfh_set_error(XFH_ERR_DEVICE, "xfh_lg_create: device %d out of range", device);
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XFH_ERR_DEVICE, "xfh_lg_create: no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(XFH_ERR_DEVICE, "xfh_lg_create: device %d out of range", device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return xfh_set_error(XFH_ERR_DEVICE, "xfh_lg_create: device %d is not gfx950", device);
-    if (hipSetDevice(device) != hipSuccess) return xfh_set_error(XFH_ERR_HIP, "xfh_lg_create: hipSetDevice failed");
+        return fail(XFH_ERR_DEVICE, "xfh_lg_create: device %d is not gfx950", device);
+    if (hipSetDevice(device) != hipSuccess) return fail(XFH_ERR_HIP, "xfh_lg_create: hipSetDevice failed");
 
     std::vector<float> blob;
     auto reserve = [&](size_t n) { size_t o = (blob.size() + 63) / 64 * 64; blob.resize(o + n, 0.f); return o; };
@@ -137,7 +135,7 @@ int xfh_lg_create(const float* const* host_arrays, int n_arrays, int device, xfh
     if (e != hipSuccess) {
         if (ctx->blob) (void)hipFree(ctx->blob);
         delete ctx;
-        return xfh_set_error(XFH_ERR_HIP, "xfh_lg_create: weight upload failed: %s", hipGetErrorString(e));
+        return fail(XFH_ERR_HIP, "xfh_lg_create: weight upload failed: %s", hipGetErrorString(e));
     }
     auto lin = [&](const LinOff& o) { LgLin l; l.w = ctx->blob + o.w; l.b = ctx->blob + o.b; l.k = o.k; l.n = o.n; return l; };
     ctx->input_proj = lin(o_in);
@@ -156,7 +154,7 @@ int xfh_lg_create(const float* const* host_arrays, int n_arrays, int device, xfh
 }
 
 int xfh_lg_profile(xfh_lg_handle h, int enable) {
-    if (!h) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_profile: NULL handle");
+    if (!h) return fail(XFH_ERR_ARG, "xfh_lg_profile: NULL handle");
     h->prof_on = enable != 0;
     h->prof_used = 0;
     h->prof_flops = 0;
@@ -164,12 +162,12 @@ int xfh_lg_profile(xfh_lg_handle h, int enable) {
 }
 
 int xfh_lg_profile_read(xfh_lg_handle h, int* n_launches, double* total_ms, double* total_flops) {
-    if (!h) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_profile_read: NULL handle");
+    if (!h) return fail(XFH_ERR_ARG, "xfh_lg_profile_read: NULL handle");
     double ms = 0;
     for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
         float t = 0;
         if (hipEventSynchronize(h->prof_ev[i + 1]) != hipSuccess || hipEventElapsedTime(&t, h->prof_ev[i], h->prof_ev[i + 1]) != hipSuccess)
-            return xfh_set_error(XFH_ERR_HIP, "xfh_lg_profile_read: event query failed");
+            return fail(XFH_ERR_HIP, "xfh_lg_profile_read: event query failed");
         ms += t;
     }
     if (n_launches) *n_launches = (int)(h->prof_used / 2);
@@ -346,20 +344,20 @@ static int lg_match_impl(xfh_lg_handle h, const float* kpts0, const float* desc0
     }
     launch_lg_assign(w.sim, w.n1pad, nn[0], N0, nn[1], N1, w.s[0].z, w.s[1].z, w.rlse, w.clse, w.m0, w.m1, w.best0, ind[0], ind[1], min_conf,
                      matches, scores, n_matches, w.ascratch, st);
-    if (bad) return xfh_set_error(XFH_ERR_UNSUPPORTED, "xfh_lg_match: missing linear kernel instantiation");
+    if (bad) return fail(XFH_ERR_UNSUPPORTED, "xfh_lg_match: missing linear kernel instantiation");
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return xfh_set_error(XFH_ERR_HIP, "xfh_lg_match: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(XFH_ERR_HIP, "xfh_lg_match: %s", hipGetErrorString(e));
     return XFH_OK;
 }
 
 int xfh_lg_match(xfh_lg_handle h, const float* kpts0, const float* desc0, int N0, float W0, float H0, const float* kpts1, const float* desc1,
                  int N1, float W1, float H1, float min_conf, int prune_min_kpts, int64_t* matches, float* scores, int32_t* n_matches,
                  void* workspace, size_t workspace_bytes, xfh_stream stream) {
-    if (!h || !kpts0 || !desc0 || !kpts1 || !desc1 || !matches || !scores || !n_matches) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match: NULL argument");
-    if (N0 <= 0 || N1 <= 0 || N0 > 16384 || N1 > 16384) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match: key-point counts must be in 1..16384");
-    if (((size_t)desc0 | (size_t)desc1) & 15) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match: descriptors must be 16-byte aligned");
+    if (!h || !kpts0 || !desc0 || !kpts1 || !desc1 || !matches || !scores || !n_matches) return fail(XFH_ERR_ARG, "xfh_lg_match: NULL argument");
+    if (N0 <= 0 || N1 <= 0 || N0 > 16384 || N1 > 16384) return fail(XFH_ERR_ARG, "xfh_lg_match: key-point counts must be in 1..16384");
+    if (((size_t)desc0 | (size_t)desc1) & 15) return fail(XFH_ERR_ARG, "xfh_lg_match: descriptors must be 16-byte aligned");
     const size_t need = xfh_lg_workspace_bytes(N0, N1);
-    if (!workspace || workspace_bytes < need || ((size_t)workspace & 255)) return xfh_set_error(XFH_ERR_WORKSPACE, "xfh_lg_match: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
+    if (!workspace || workspace_bytes < need || ((size_t)workspace & 255)) return fail(XFH_ERR_WORKSPACE, "xfh_lg_match: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
     return lg_match_impl(h, kpts0, desc0, N0, nullptr, W0, H0, kpts1, desc1, N1, nullptr, W1, H1, min_conf, prune_min_kpts, matches, scores,
                          n_matches, workspace, (hipStream_t)stream);
 }
@@ -367,11 +365,11 @@ int xfh_lg_match(xfh_lg_handle h, const float* kpts0, const float* desc0, int N0
 int xfh_lg_match_pairs(xfh_lg_handle h, const float* kpts, const float* desc, const int32_t* counts, int P, int cap, float W, float H,
                        float min_conf, int prune_min_kpts, int64_t* matches, float* scores, int32_t* n_matches, void* workspace,
                        size_t workspace_bytes, xfh_stream stream) {
-    if (!h || !kpts || !desc || !counts || !matches || !scores || !n_matches) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match_pairs: NULL argument");
-    if (P <= 0 || cap <= 0 || cap > 16384) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match_pairs: need P > 0 and 1 <= cap <= 16384");
-    if ((size_t)desc & 15) return xfh_set_error(XFH_ERR_ARG, "xfh_lg_match_pairs: descriptors must be 16-byte aligned");
+    if (!h || !kpts || !desc || !counts || !matches || !scores || !n_matches) return fail(XFH_ERR_ARG, "xfh_lg_match_pairs: NULL argument");
+    if (P <= 0 || cap <= 0 || cap > 16384) return fail(XFH_ERR_ARG, "xfh_lg_match_pairs: need P > 0 and 1 <= cap <= 16384");
+    if ((size_t)desc & 15) return fail(XFH_ERR_ARG, "xfh_lg_match_pairs: descriptors must be 16-byte aligned");
     const size_t need = xfh_lg_workspace_bytes(cap, cap);
-    if (!workspace || workspace_bytes < need || ((size_t)workspace & 255)) return xfh_set_error(XFH_ERR_WORKSPACE, "xfh_lg_match_pairs: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
+    if (!workspace || workspace_bytes < need || ((size_t)workspace & 255)) return fail(XFH_ERR_WORKSPACE, "xfh_lg_match_pairs: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
     for (int p = 0; p < P; ++p) {           // pairs run back to back on the stream and share the workspace
         const size_t f0 = 2 * (size_t)p, f1 = f0 + 1;
         const int rc = lg_match_impl(h, kpts + f0 * cap * 2, desc + f0 * cap * 64, cap, counts + f0, W, H, kpts + f1 * cap * 2, desc + f1 * cap * 64,

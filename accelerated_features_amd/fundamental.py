@@ -14,7 +14,7 @@ use ``homography.find_homography`` there.  There is no CPU path: without the HIP
 import torch
 
 from . import _lib, _twoview
-from ._twoview import ptr as _ptr
+from ._twoview import WORKSPACE_LIMIT, ptr as _ptr
 
 FM_7POINT = 1             # cv2.FM_7POINT: exactly 7 points, every real solution (up to 3, stacked)
 FM_8POINT = 2             # cv2.FM_8POINT: one least-squares fit on all points (at least 8)
@@ -22,7 +22,6 @@ USAC_MAGSAC = 38          # cv2.USAC_MAGSAC: the robust estimator, and this modu
 METHODS = (FM_7POINT, FM_8POINT, USAC_MAGSAC)
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "score_lo", "score_hi")
 MAX_ITERATIONS = 16384                       # the kernel's limit; more is an error
-WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs
 _WHAT = "fundamental matrix estimation"
 
 

@@ -15,13 +15,11 @@ import ctypes as C
 
 import torch
 
-from . import _lib, _twoview, absolute_pose, guided as _guided
+from . import _lib, _scenes, _twoview, absolute_pose, guided as _guided
+from ._scenes import MAX_SCENES, MAX_VIEWS, WORKSPACE_LIMIT      # noqa: F401 (public here)
 from ._twoview import ptr as _ptr
 
 MAP_INFO_FIELDS = ("tracks", "written", "skipped_status", "skipped_point", "skipped_views", "skipped_norm", "over_capacity", "spare")
-MAX_VIEWS = 32
-MAX_SCENES = 65535                           # of one library call; larger batches are split into chunks of scenes
-WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of scenes
 _WHAT = "map building"
 
 
@@ -84,10 +82,7 @@ def build_map_batch(desc, tracks, points3d, status, inlier_views, min_views=2, m
                                  int(min_views), M, _ptr(out['points'][a:b]), _ptr(out['desc'][a:b]), _ptr(out['desc_f16'][a:b]), _ptr(out['track'][a:b]),
                                  _ptr(out['n_obs'][a:b]), _ptr(out['coherence'][a:b]), _ptr(out['n_points'][a:b]), _ptr(out['info'][a:b]), ws, ws_bytes,
                                  stream)
-    for a in range(0, S, MAX_SCENES):         # chunks of 65535 scenes, each split under the workspace limit
-        b = min(S, a + MAX_SCENES)
-        _twoview.run_chunked("xfh_build_map", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_map_workspace_bytes(n, T, V), dev,
-                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    _scenes.run_scenes("xfh_build_map", S, lambda n: lib.xfh_map_workspace_bytes(n, T, V), dev, call)
     return out
 
 
@@ -118,7 +113,7 @@ def project_map(points, n_points, R, t, K, image_size=None, margin=0.0):
     R, t = torch.as_tensor(R, dtype=torch.float64), torch.as_tensor(t, dtype=torch.float64)
     if R.shape != (Q, 3, 3) or t.shape != (Q, 3):
         raise RuntimeError('expected R (Q,3,3) and t (Q,3)')
-    R, t, K = R.to(dev).contiguous(), t.to(dev).contiguous(), absolute_pose._intrinsics(K, Q, dev)
+    R, t, K = R.to(dev).contiguous(), t.to(dev).contiguous(), _twoview.intrinsics(K, Q, dev)
     uv = torch.empty((Q, M, 2), dtype=torch.float32, device=dev)
     if Q == 0 or M == 0:
         return uv
@@ -168,9 +163,7 @@ def localize_map_batch(kpts_q, desc_q, n_q, map, K, scene_of=None, min_cossim=0.
     who = "localize_map_batch"
     if not isinstance(map, dict) or any(k not in map for k in _MAP_KEYS):
         raise RuntimeError(f'{who}: map must be the dict of build_map_batch')
-    for t in (kpts_q, desc_q, n_q) + tuple(map[k] for k in _MAP_KEYS):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, kpts_q, desc_q, n_q, *(map[k] for k in _MAP_KEYS))
     if desc_q.dim() != 3 or desc_q.shape[2] != 64 or kpts_q.shape != desc_q.shape[:2] + (2,) or n_q.shape != desc_q.shape[:1]:
         raise RuntimeError('expected kpts_q (Q,Kq,2), desc_q (Q,Kq,64) and n_q (Q,)')
     Q, Kq = desc_q.shape[:2]
@@ -203,7 +196,7 @@ def localize_map_batch(kpts_q, desc_q, n_q, map, K, scene_of=None, min_cossim=0.
         sc = scene_of.to(dev).clamp(0, max(S - 1, 0))
         mp, md, m16, mt, mn = (x[sc].contiguous() for x in (mp, md, m16, mt, mn))
     cap = min(Kq, M)
-    K = absolute_pose._intrinsics(K, Q, dev)
+    K = _twoview.intrinsics(K, Q, dev)
 
     def lists(i_q, i_m, n):
         """The first cap entries (no list is longer) and the track of every match."""

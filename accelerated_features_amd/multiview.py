@@ -24,23 +24,13 @@ import math
 
 import torch
 
-from . import _lib, _twoview
+from . import _lib, _scenes, _twoview
+from ._scenes import MAX_SCENES, MAX_VIEWS, WORKSPACE_LIMIT      # noqa: F401 (public here)
 from ._twoview import ptr as _ptr
 
 STATUS = ("valid", "unobserved", "not_finite", "behind", "far", "reproj", "parallax")      # the status codes 0 .. 6
 INFO_FIELDS = ("n", "valid", "unobserved", "not_finite", "behind", "far", "reproj", "parallax")
-MAX_VIEWS = 32
-MAX_SCENES = 65535                           # of one library call; larger batches are split into chunks of scenes
 _WHAT = "multi-view triangulation"
-
-
-def _chunks(S):
-    return [(a, min(S, a + MAX_SCENES)) for a in range(0, S, MAX_SCENES)]
-
-
-def _views(who, V):
-    if not 2 <= V <= MAX_VIEWS:
-        raise _lib.XFeatHipError(f"{who}: V {V} outside [2, {MAX_VIEWS}]")
 
 
 def build_tracks(idx_ref, idx_view, n_matches, K):
@@ -51,16 +41,14 @@ def build_tracks(idx_ref, idx_view, n_matches, K):
     Returns tracks (S, K, V) int32: [s, k, 0] = k, [s, k, v] = the row of view v that reference row k is matched to, or -1.  An index
     outside [0, K) is ignored; of duplicate reference rows the largest candidate row stays (the table is reproducible).  Asynchronous."""
     who = "build_tracks"
-    for t in (idx_ref, idx_view, n_matches):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, idx_ref, idx_view, n_matches)
     if idx_ref.dim() != 3 or idx_view.shape != idx_ref.shape or n_matches.shape != idx_ref.shape[:2]:
         raise RuntimeError('expected idx_ref, idx_view (S,V-1,cap) and n_matches (S,V-1)')
     S, V, cap = idx_ref.shape[0], idx_ref.shape[1] + 1, idx_ref.shape[2]
     K = int(K)
     if K < 0:
         raise RuntimeError(f'{who}: K {K} is negative')
-    _views(who, V)
+    _scenes.views(who, V)
     if not idx_ref.is_cuda:
         raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
     for t, dt in ((idx_ref, torch.int64), (idx_view, torch.int64), (n_matches, torch.int32)):
@@ -72,17 +60,10 @@ def build_tracks(idx_ref, idx_view, n_matches, K):
         return tracks
     lib = _lib.load()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    for a, b in _chunks(S):
+    for a, b in _scenes.chunks(S):
         _lib.check(lib.xfh_build_tracks(_ptr(idx_ref[a:b]) if cap else None, _ptr(idx_view[a:b]) if cap else None, _ptr(n_matches[a:b]) if cap else None,
                                         b - a, V, cap, K, K, _ptr(tracks[a:b]), stream), "xfh_build_tracks")
     return tracks
-
-
-def _f64(x, shape, dev, name):
-    x = torch.as_tensor(x, dtype=torch.float64)
-    if x.shape != shape:
-        raise RuntimeError(f'{name} must be {tuple(shape)}')
-    return x.to(dev).contiguous()
 
 
 def _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views):
@@ -131,19 +112,12 @@ def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=
     thr, cos_min, depth, min_views = _gates(who, max_reproj_error, min_parallax_deg, max_depth, min_views)
     entry = _anchor(who, anchor)
     kpts, tracks = torch.as_tensor(kpts), torch.as_tensor(tracks)
-    if kpts.dim() != 4 or kpts.shape[3] != 2 or tracks.dim() != 3 or tracks.shape[0] != kpts.shape[0] or tracks.shape[2] != kpts.shape[1]:
-        raise RuntimeError('expected kpts (S,V,Kcap,2) and tracks (S,K,V)')
-    S, V, kcap = kpts.shape[:3]
-    K = tracks.shape[1]
-    _views(who, V)
+    S, V, kcap, K = _scenes.kpts_tracks(kpts, tracks)
+    _scenes.views(who, V)
     dev = kpts.device if kpts.is_cuda else _twoview.device(_WHAT)
     kpts, tracks = kpts.to(dev).float().contiguous(), tracks.to(dev).to(torch.int32).contiguous()
-    if n_views is not None:
-        n_views = torch.as_tensor(n_views)
-        if n_views.shape != (S,):
-            raise RuntimeError('n_views must have one entry per scene')
-        n_views = n_views.to(dev).to(torch.int32).contiguous()
-    Ks, Rs, ts = _f64(Ks, (S, V, 3, 3), dev, 'Ks'), _f64(Rs, (S, V, 3, 3), dev, 'Rs'), _f64(ts, (S, V, 3), dev, 'ts')
+    n_views = _scenes.n_views_arg(n_views, S, dev)
+    Ks, Rs, ts = _scenes.f64(Ks, (S, V, 3, 3), dev, 'Ks'), _scenes.f64(Rs, (S, V, 3, 3), dev, 'Rs'), _scenes.f64(ts, (S, V, 3), dev, 'ts')
     X = torch.empty((S, K, 3), dtype=torch.float32, device=dev)
     status = torch.empty((S, K), dtype=torch.uint8, device=dev)
     ninl = torch.empty((S, K), dtype=torch.uint8, device=dev)
@@ -158,7 +132,7 @@ def triangulate_views_batch(kpts, tracks, n_views, Ks, Rs, ts, max_reproj_error=
     else:
         lib = _lib.load()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        for a, b in _chunks(S):
+        for a, b in _scenes.chunks(S):
             _lib.check(getattr(lib, entry)(_ptr(kpts[a:b]), kcap, _ptr(tracks[a:b]), _ptr(n_views[a:b]) if n_views is not None else None, b - a, K, V,
                                            _ptr(Ks[a:b]), _ptr(Rs[a:b]), _ptr(ts[a:b]), thr, cos_min, depth, min_views, _ptr(X[a:b]), _ptr(status[a:b]),
                                            _ptr(ninl[a:b]), _ptr(inl[a:b]), _ptr(err[a:b]), _ptr(info[a:b]), stream), entry)
@@ -185,7 +159,6 @@ BA_STATUS = ("ok", "nothing_to_refine", "not_finite")       # info[:, 5]
 BA_INFO_FIELDS = ("refined_points", "observations", "free_views", "iterations", "accepted_steps", "status", "spare0", "spare1")
 MIN_VIEW_OBS = 6                             # ba::MIN_VIEW_OBS: a view with fewer observations is held
 MAX_BA_ITERATIONS = 1000
-WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of scenes
 
 
 def _ba_settings(who, fixed_views, max_iterations, huber_px):
@@ -219,22 +192,15 @@ def bundle_adjust_batch(kpts, tracks, inlier_views, points3d, n_views, Ks, Rs, t
     fixed_views, iters, huber = _ba_settings(who, fixed_views, max_iterations, huber_px)
     kpts, tracks = torch.as_tensor(kpts), torch.as_tensor(tracks)
     inlier_views, points3d = torch.as_tensor(inlier_views), torch.as_tensor(points3d)
-    if kpts.dim() != 4 or kpts.shape[3] != 2 or tracks.dim() != 3 or tracks.shape[0] != kpts.shape[0] or tracks.shape[2] != kpts.shape[1]:
-        raise RuntimeError('expected kpts (S,V,Kcap,2) and tracks (S,K,V)')
-    S, V, kcap = kpts.shape[:3]
-    K = tracks.shape[1]
+    S, V, kcap, K = _scenes.kpts_tracks(kpts, tracks)
     if inlier_views.shape != (S, K) or points3d.shape != (S, K, 3):
         raise RuntimeError('expected inlier_views (S,K) and points3d (S,K,3)')
-    _views(who, V)
+    _scenes.views(who, V)
     dev = kpts.device if kpts.is_cuda else _twoview.device("bundle adjustment")
     kpts, tracks = kpts.to(dev).float().contiguous(), tracks.to(dev).to(torch.int32).contiguous()
     inlier_views, points3d = inlier_views.to(dev).to(torch.int32).contiguous(), points3d.to(dev).float().contiguous()
-    if n_views is not None:
-        n_views = torch.as_tensor(n_views)
-        if n_views.shape != (S,):
-            raise RuntimeError('n_views must have one entry per scene')
-        n_views = n_views.to(dev).to(torch.int32).contiguous()
-    Ks, Rs, ts = _f64(Ks, (S, V, 3, 3), dev, 'Ks'), _f64(Rs, (S, V, 3, 3), dev, 'Rs'), _f64(ts, (S, V, 3), dev, 'ts')
+    n_views = _scenes.n_views_arg(n_views, S, dev)
+    Ks, Rs, ts = _scenes.f64(Ks, (S, V, 3, 3), dev, 'Ks'), _scenes.f64(Rs, (S, V, 3, 3), dev, 'Rs'), _scenes.f64(ts, (S, V, 3), dev, 'ts')
     if S == 0 or K == 0 or kcap == 0:         # no observation at all: nothing to refine
         info = torch.zeros((S, 8), dtype=torch.int32, device=dev)
         info[:, 5] = 1
@@ -253,9 +219,7 @@ def bundle_adjust_batch(kpts, tracks, inlier_views, points3d, n_views, Ks, Rs, t
                                      _ptr(n_views[a:b]) if n_views is not None else None, b - a, K, V, _ptr(Ks[a:b]), _ptr(Rs[a:b]), _ptr(ts[a:b]),
                                      fixed_views, iters, huber, _ptr(Ro[a:b]), _ptr(to[a:b]), _ptr(Xo[a:b]), _ptr(refined[a:b]), _ptr(free[a:b]),
                                      _ptr(cost[a:b]), _ptr(info[a:b]), ws, ws_bytes, stream)
-    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
-        _twoview.run_chunked("xfh_bundle_adjust", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_bundle_workspace_bytes(n, K, V), dev,
-                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    _scenes.run_scenes("xfh_bundle_adjust", S, lambda n: lib.xfh_bundle_workspace_bytes(n, K, V), dev, call)
     return {'Rs': Ro, 'ts': to, 'points3d': Xo, 'refined': refined.bool(), 'free_views': free, 'cost': cost, 'info': info}
 
 
@@ -295,18 +259,15 @@ def build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, n_views, K, min_leng
     Returns (tracks (S, T, V) int32: a row or -1, rows >= n_tracks[s] all -1;  track_of (S, V, K) int32: the track of a key-point or -1;
     n_tracks (S,) int32;  info (S, 8) int32: TRACK_INFO_FIELDS, status: TRACK_STATUS).  Asynchronous."""
     who = "build_tracks_graph"
-    for t in (view_pairs, idx_a, idx_b, n_matches):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, view_pairs, idx_a, idx_b, n_matches)
     V, K = int(n_views), int(K)
     if K < 0:
         raise RuntimeError(f'{who}: K {K} is negative')
-    _views(who, V)
+    _scenes.views(who, V)
     if idx_a.dim() != 3 or idx_b.shape != idx_a.shape or n_matches.shape != idx_a.shape[:2]:
         raise RuntimeError('expected idx_a, idx_b (S,P,cap) and n_matches (S,P)')
     S, P, cap = idx_a.shape
-    if view_pairs.shape not in ((S, P, 2), (P, 2)):
-        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    _scenes.check_view_pairs(view_pairs, S, P)
     if P > MAX_PAIRS:
         raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_PAIRS}")
     if not 2 <= int(min_length) <= MAX_VIEWS:
@@ -335,9 +296,7 @@ def build_tracks_graph(view_pairs, idx_a, idx_b, n_matches, n_views, K, min_leng
         return lib.xfh_build_tracks_graph(_ptr(view_pairs[a:b]), _ptr(idx_a[a:b]), _ptr(idx_b[a:b]), _ptr(n_matches[a:b]), b - a, P, cap, V, K,
                                           int(min_length), T, _ptr(tracks[a:b]), _ptr(track_of[a:b]), _ptr(n_tracks[a:b]), _ptr(info[a:b]), ws,
                                           ws_bytes, stream)
-    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
-        _twoview.run_chunked("xfh_build_tracks_graph", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_track_graph_workspace_bytes(n, V, K), dev,
-                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    _scenes.run_scenes("xfh_build_tracks_graph", S, lambda n: lib.xfh_track_graph_workspace_bytes(n, V, K), dev, call)
     return tracks, track_of, n_tracks, info
 
 
@@ -448,10 +407,7 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
     if R_rel.dim() != 4 or R_rel.shape[2:] != (3, 3):
         raise RuntimeError('expected R_rel (S,P,3,3)')
     S, P = R_rel.shape[:2]
-    if t_rel.shape != (S, P, 3) or weight.shape != (S, P):
-        raise RuntimeError('expected t_rel (S,P,3) and weight (S,P)')
-    if view_pairs.shape not in ((S, P, 2), (P, 2)):
-        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    _scenes.check_edges(view_pairs, t_rel, weight, S, P)
     per_scene = torch.is_tensor(n_views)
     if per_scene:
         if V is None:
@@ -459,14 +415,11 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
         if n_views.shape != (S,):
             raise RuntimeError('n_views must have one entry per scene')
     V = int(n_views) if not per_scene else int(V)
-    _views(who, V)
+    _scenes.views(who, V)
     if P > MAX_PG_PAIRS:
         raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_PG_PAIRS}")
     dev = R_rel.device if R_rel.is_cuda else _twoview.device("pose-graph initialisation")
-    if view_pairs.dim() == 2:
-        view_pairs = view_pairs.expand(S, P, 2)
-    view_pairs = view_pairs.to(dev).to(torch.int32).contiguous()
-    R_rel, t_rel, weight = (x.to(dev).to(torch.float64).contiguous() for x in (R_rel, t_rel, weight))
+    view_pairs, R_rel, t_rel, weight = _scenes.edges_arg(view_pairs, R_rel, t_rel, weight, S, P, dev)
     n_views = n_views.to(dev).to(torch.int32).contiguous() if per_scene else None
     Rs = torch.empty((S, V, 3, 3), dtype=torch.float64, device=dev)
     ts = torch.empty((S, V, 3), dtype=torch.float64, device=dev)
@@ -501,8 +454,7 @@ def average_poses_batch(view_pairs, R_rel, t_rel, weight, n_views, iterations=30
     name, run, size = "xfh_average_poses", call, lib.xfh_pose_graph_workspace_bytes
     if ratio is not None:
         name, run, size = "xfh_average_poses_ratios", call_ratios, lib.xfh_pose_graph_ratios_workspace_bytes
-    for a, b in _chunks(S):                   # chunks of 65535 scenes, each split under the workspace limit
-        _twoview.run_chunked(name, b - a, WORKSPACE_LIMIT, lambda n: size(n, P, V), dev, lambda c, d, ws, nb, st, a=a: run(a + c, a + d, ws, nb, st))
+    _scenes.run_scenes(name, S, lambda n: size(n, P, V), dev, run)
     return out
 
 
@@ -521,13 +473,11 @@ def baseline_ratios_batch(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weig
     entry when there is no edge, no key-point row or no track row (written without a library call, info 0).  Asynchronous."""
     who = "baseline_ratios_batch"
     thr, cos_min, depth, _ = _gates(who, max_reproj_error, min_parallax_deg, max_depth, 2)
-    for t in (kpts, tracks, track_of):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, kpts, tracks, track_of)
     if kpts.dim() != 4 or kpts.shape[3] != 2:
         raise RuntimeError('expected kpts (S,V,K,2)')
     S, V, K = kpts.shape[:3]
-    _views(who, V)
+    _scenes.views(who, V)
     if tracks.dim() != 3 or tracks.shape[0] != S or tracks.shape[2] != V or track_of.shape != (S, V, K):
         raise RuntimeError('expected tracks (S,T,V) and track_of (S,V,K) for kpts (S,V,K,2)')
     T = tracks.shape[1]
@@ -535,10 +485,7 @@ def baseline_ratios_batch(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weig
     if R_rel.dim() != 4 or R_rel.shape[0] != S or R_rel.shape[2:] != (3, 3):
         raise RuntimeError('expected R_rel (S,P,3,3)')
     P = R_rel.shape[1]
-    if t_rel.shape != (S, P, 3) or weight.shape != (S, P):
-        raise RuntimeError('expected t_rel (S,P,3) and weight (S,P)')
-    if view_pairs.shape not in ((S, P, 2), (P, 2)):
-        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    _scenes.check_edges(view_pairs, t_rel, weight, S, P)
     if P > MAX_RATIO_PAIRS:
         raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_RATIO_PAIRS}")
     if K > MAX_RATIO_KPTS:
@@ -549,16 +496,9 @@ def baseline_ratios_batch(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weig
     for t, dt, name in ((kpts, torch.float32, 'kpts'), (tracks, torch.int32, 'tracks'), (track_of, torch.int32, 'track_of')):
         if t.dtype != dt or not t.is_contiguous() or t.device != dev:
             raise RuntimeError(f'{who}: {name} must be a contiguous {dt} tensor on the device of kpts')
-    if n_views is not None:
-        n_views = torch.as_tensor(n_views)
-        if n_views.shape != (S,):
-            raise RuntimeError('n_views must have one entry per scene')
-        n_views = n_views.to(dev).to(torch.int32).contiguous()
-    Ks = _f64(Ks, (S, V, 3, 3), dev, 'Ks')
-    if view_pairs.dim() == 2:
-        view_pairs = view_pairs.expand(S, P, 2)
-    view_pairs = view_pairs.to(dev).to(torch.int32).contiguous()
-    R_rel, t_rel, weight = (x.to(dev).to(torch.float64).contiguous() for x in (R_rel, t_rel, weight))
+    n_views = _scenes.n_views_arg(n_views, S, dev)
+    Ks = _scenes.f64(Ks, (S, V, 3, 3), dev, 'Ks')
+    view_pairs, R_rel, t_rel, weight = _scenes.edges_arg(view_pairs, R_rel, t_rel, weight, S, P, dev)
     ratio = torch.empty((S, P, P), dtype=torch.float64, device=dev)
     count = torch.empty((S, P, P), dtype=torch.int32, device=dev)
     shared = torch.empty((S, P, P), dtype=torch.int32, device=dev)
@@ -576,9 +516,7 @@ def baseline_ratios_batch(kpts, tracks, track_of, view_pairs, R_rel, t_rel, weig
                                        _ptr(weight[a:b]), _ptr(Ks[a:b]), _ptr(n_views[a:b]) if n_views is not None else None, b - a, P, V, K, T, thr,
                                        cos_min, depth, int(min_common), _ptr(ratio[a:b]), _ptr(count[a:b]), _ptr(shared[a:b]), _ptr(info[a:b]), ws,
                                        ws_bytes, stream)
-    for a, b in _chunks(S):
-        _twoview.run_chunked("xfh_baseline_ratios", b - a, WORKSPACE_LIMIT, lambda n: lib.xfh_baseline_ratios_workspace_bytes(n, P, V, K), dev,
-                             lambda c, d, ws, nb, st, a=a: call(a + c, a + d, ws, nb, st))
+    _scenes.run_scenes("xfh_baseline_ratios", S, lambda n: lib.xfh_baseline_ratios_workspace_bytes(n, P, V, K), dev, call)
     return out
 
 
@@ -593,24 +531,21 @@ def relative_poses_graph_matches(kpts, view_pairs, idx_a, idx_b, n_matches, Ks, 
     uint8, 'info' (S,P,8) int32 (pose.INFO_FIELDS): the arguments of ``average_poses_batch``.  Asynchronous."""
     from . import pose
     who = "relative_poses_graph_matches"
-    for t in (kpts, view_pairs, idx_a, idx_b, n_matches):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, kpts, view_pairs, idx_a, idx_b, n_matches)
     if kpts.dim() != 4 or kpts.shape[3] != 2:
         raise RuntimeError('expected kpts (S,V,K,2)')
     S, V, K = kpts.shape[:3]
-    _views(who, V)
+    _scenes.views(who, V)
     if idx_a.dim() != 3 or idx_a.shape[0] != S or idx_b.shape != idx_a.shape or n_matches.shape != idx_a.shape[:2]:
         raise RuntimeError('expected idx_a, idx_b (S,P,cap) and n_matches (S,P) for kpts (S,V,K,2)')
     P, cap = idx_a.shape[1:]
-    if view_pairs.shape not in ((S, P, 2), (P, 2)):
-        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    _scenes.check_view_pairs(view_pairs, S, P)
     if int(min_inliers) < 0:
         raise _lib.XFeatHipError(f"{who}: min_inliers {min_inliers} is negative")
     if not kpts.is_cuda:
         raise _lib.XFeatHipError(f"{who} works on device-resident match lists")
     dev = kpts.device
-    Ks = _f64(Ks, (S, V, 3, 3), dev, 'Ks')
+    Ks = _scenes.f64(Ks, (S, V, 3, 3), dev, 'Ks')
     vp = (view_pairs.expand(S, P, 2) if view_pairs.dim() == 2 else view_pairs).to(dev).long()
     a, b = vp[..., 0], vp[..., 1]
     legal = (a != b) & (a >= 0) & (a < V) & (b >= 0) & (b < V)

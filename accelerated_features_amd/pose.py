@@ -24,24 +24,14 @@ import numpy as np
 import torch
 
 from . import _lib, _twoview
-from ._twoview import chunk_seed, ptr as _ptr           # chunk_seed is public here: pose.chunk_seed(seed, p) = the seed of pair p alone
+from ._twoview import WORKSPACE_LIMIT, chunk_seed, intrinsics as _intrinsics, ptr as _ptr      # chunk_seed is public here: pose.chunk_seed(seed, p) = the seed of pair p alone
 
 INFO_FIELDS = ("found", "best_it", "iters", "n_inliers", "lo_accepted", "n", "cost_lo", "cost_hi")
 MAX_ITERATIONS = 16384                       # the kernel's limit; more is an error
 MAX_THRESHOLDS = 16                          # of one sweep call; more is an error
 SCANNET_THRESHOLDS = (0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5, 4.0, 4.5, 5.0, 5.5, 6.0)   # 'ransac_thresholds' of modules/eval/scannet1500.py
-WORKSPACE_LIMIT = 512 << 20                  # bytes of workspace per library call: larger batches are split into chunks of pairs
 _WHAT = "relative pose estimation"
 RANSAC_DEFAULTS = {"max_epipolar_error": 1.0, "success_prob": 0.99999, "min_iterations": 20, "max_iterations": 10000}
-
-
-def _intrinsics(K, P, dev):
-    K = torch.as_tensor(K, dtype=torch.float64)
-    if K.shape == (3, 3):
-        K = K.expand(P, 3, 3)
-    if K.shape != (P, 3, 3):
-        raise RuntimeError('intrinsics must be (3,3) or (P,3,3)')
-    return K.to(dev).contiguous()
 
 
 def _run(who, pts0, pts1, index, counts, n_const, P, cap, K0, K1, max_epipolar_error, success_prob, min_iterations, max_iterations, seed, dev):

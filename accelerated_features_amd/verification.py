@@ -15,15 +15,14 @@ import math
 
 import torch
 
-from . import _lib, _twoview
+from . import _lib, _scenes
+from ._scenes import MAX_SCENES, MAX_VIEWS      # noqa: F401 (public here)
 from ._twoview import ptr as _ptr
 
 FILTER_INFO_FIELDS = ("read", "set", "emptied", "spare")
 EMPTIED = ("no", "keep", "min_keep")                       # filter info[..., 2]
 VERIFY_INFO_FIELDS = ("status", "read", "kept", "spare")
 VERIFY_STATUS = ("ok", "illegal_pair", "pose_not_usable", "zero_baseline")       # verify info[..., 0]
-MAX_VIEWS = 32
-MAX_SCENES = 65535                           # of one xfh_verify_matches call; larger batches are split into chunks of scenes
 MAX_PAIRS = 65535
 MAX_LISTS = (1 << 31) - 1                    # of one xfh_filter_matches call; larger batches are split into chunks of lists
 MAX_CAP = 1 << 24
@@ -41,14 +40,11 @@ def filter_matches_batch(idx_a, idx_b, n_matches, mask, keep=None, min_keep=0):
     FILTER_INFO_FIELDS = entries read, entries whose mask is set, the reason the list was emptied (EMPTIED), 0.  Two calls give the same
     bytes.  Asynchronous: nothing synchronises with the host."""
     who = "filter_matches_batch"
-    for t in (idx_a, idx_b, n_matches, mask):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, idx_a, idx_b, n_matches, mask)
     if idx_a.dim() not in (2, 3) or idx_b.shape != idx_a.shape or mask.shape != idx_a.shape or n_matches.shape != idx_a.shape[:-1]:
         raise RuntimeError('expected idx_a, idx_b, mask (P,cap) or (S,P,cap) and n_matches (P,) or (S,P)')
     if keep is not None:
-        if not torch.is_tensor(keep):
-            raise RuntimeError(f'{who}: tensors expected')
+        _scenes.tensors(who, keep)
         if keep.shape != n_matches.shape:
             raise RuntimeError('keep must have one entry per list')
     if isinstance(min_keep, bool) or int(min_keep) != min_keep or int(min_keep) < 0:
@@ -105,19 +101,15 @@ def verify_matches_graph(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks,
     Returns (mask (S,P,cap) uint8, 0 wherever nothing was evaluated;  err (S,P,cap) float32, the Sampson error in pixels, NaN wherever
     nothing was evaluated;  info (S,P,4) int32: VERIFY_INFO_FIELDS = status, entries read, entries kept, 0).  Asynchronous."""
     who = "verify_matches_graph"
-    for t in (kpts, view_pairs, idx_a, idx_b, n_matches):
-        if not torch.is_tensor(t):
-            raise RuntimeError(f'{who}: tensors expected')
+    _scenes.tensors(who, kpts, view_pairs, idx_a, idx_b, n_matches)
     if kpts.dim() != 4 or kpts.shape[3] != 2:
         raise RuntimeError('expected kpts (S,V,K,2)')
     S, V, K = kpts.shape[:3]
-    if not 2 <= V <= MAX_VIEWS:
-        raise _lib.XFeatHipError(f"{who}: V {V} outside [2, {MAX_VIEWS}]")
+    _scenes.views(who, V)
     if idx_a.dim() != 3 or idx_a.shape[0] != S or idx_b.shape != idx_a.shape or n_matches.shape != idx_a.shape[:2]:
         raise RuntimeError('expected idx_a, idx_b (S,P,cap) and n_matches (S,P) for kpts (S,V,K,2)')
     P, cap = idx_a.shape[1:]
-    if view_pairs.shape not in ((S, P, 2), (P, 2)):
-        raise RuntimeError('expected view_pairs (S,P,2) or (P,2)')
+    _scenes.check_view_pairs(view_pairs, S, P)
     if P > MAX_PAIRS:
         raise _lib.XFeatHipError(f"{who}: {P} pairs, more than {MAX_PAIRS}")
     if cap > MAX_CAP or K > MAX_CAP:
@@ -132,15 +124,9 @@ def verify_matches_graph(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks,
     for t, dt, name in ((kpts, torch.float32, 'kpts'), (idx_a, torch.int64, 'idx_a'), (idx_b, torch.int64, 'idx_b'), (n_matches, torch.int32, 'n_matches')):
         if t.dtype != dt or not t.is_contiguous() or t.device != dev:
             raise RuntimeError(f'{who}: {name} must be a contiguous {dt} tensor on the device of kpts')
-    if n_views is not None:
-        n_views = torch.as_tensor(n_views)
-        if n_views.shape != (S,):
-            raise RuntimeError('n_views must have one entry per scene')
-        n_views = n_views.to(dev).to(torch.int32).contiguous()
-    Ks, Rs, ts = _f64(Ks, (S, V, 3, 3), dev, 'Ks'), _f64(Rs, (S, V, 3, 3), dev, 'Rs'), _f64(ts, (S, V, 3), dev, 'ts')
-    if view_pairs.dim() == 2:
-        view_pairs = view_pairs.expand(S, P, 2)
-    view_pairs = view_pairs.to(dev).to(torch.int32).contiguous()
+    n_views = _scenes.n_views_arg(n_views, S, dev)
+    Ks, Rs, ts = _scenes.f64(Ks, (S, V, 3, 3), dev, 'Ks'), _scenes.f64(Rs, (S, V, 3, 3), dev, 'Rs'), _scenes.f64(ts, (S, V, 3), dev, 'ts')
+    view_pairs = _scenes.view_pairs_arg(view_pairs, S, P, dev)
     mask = torch.empty((S, P, cap), dtype=torch.uint8, device=dev)
     err = torch.empty((S, P, cap), dtype=torch.float32, device=dev)
     info = torch.empty((S, P, 4), dtype=torch.int32, device=dev)
@@ -157,10 +143,3 @@ def verify_matches_graph(kpts, view_pairs, idx_a, idx_b, n_matches, n_views, Ks,
                                           _ptr(n_views[c:d]) if n_views is not None else None, d - c, P, cap, V, K, _ptr(Ks[c:d]), _ptr(Rs[c:d]),
                                           _ptr(ts[c:d]), thr, _ptr(mask[c:d]), _ptr(err[c:d]), _ptr(info[c:d]), stream), "xfh_verify_matches")
     return mask, err, info
-
-
-def _f64(x, shape, dev, name):
-    x = torch.as_tensor(x, dtype=torch.float64)
-    if x.shape != shape:
-        raise RuntimeError(f'{name} must be {tuple(shape)}')
-    return x.to(dev).contiguous()
