@@ -13,4 +13,5 @@ from .multiview import build_tracks_graph, triangulate_graph_matches, view_point
 from .multiview import average_poses_batch, relative_poses_graph_matches, reconstruct_graph_matches  # noqa: F401
 from .multiview import baseline_ratios_batch  # noqa: F401
 from .localization import build_map_batch, localize_map_batch, project_map, resect_views_batch  # noqa: F401
+from .retrieval import global_descriptors_batch, retrieve_topk, select_pairs, train_codebook  # noqa: F401
 from .verification import filter_matches_batch, verify_matches_graph  # noqa: F401

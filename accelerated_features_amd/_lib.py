@@ -94,6 +94,13 @@ SIGNATURES = {
     "xfh_map_project": (_i, [_p, _p, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p]),
     "xfh_filter_matches": (_i, [_p, _p, _p, _p, _p, C.c_int64, _i, _i, _p, _p, _p, _p, _p, _p]),
     "xfh_verify_matches": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, C.c_double, _p, _p, _p, _p]),
+    "xfh_vlad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_vlad": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_kmeans_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_kmeans_step": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "xfh_retrieve_workspace_bytes": (_sz, [_i, _i, _i]),
+    "xfh_retrieve_topk": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "xfh_pairs_from_shortlists": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "xfh_fundamental_workspace_bytes": (_sz, [_i, _i]),
     "xfh_find_fundamental": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "xfh_find_fundamental_matches": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, _i, C.c_double, C.c_uint64, _p, _p, _p, _p, _sz,

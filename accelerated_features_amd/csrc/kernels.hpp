@@ -179,6 +179,18 @@ int launch_build_map(const float* desc, int kcap, const int32_t* tracks, const f
                      unsigned char* n_obs, float* coherence, int32_t* n_points, int32_t* info, void* ws, hipStream_t st);
 int launch_map_project(const float* points, const int32_t* n_points, int Q, int M, const double* R, const double* t, const double* K, double width,
                        double height, double margin, float* uv, hipStream_t st);
+// ---- k_retrieval.hip (image retrieval: VLAD descriptors over a k-means codebook, top-k shortlists, pair lists from shortlists) ----
+size_t vlad_workspace_bytes(int G, int K, int C);
+size_t kmeans_workspace_bytes(int G, int K, int C);
+size_t retrieve_workspace_bytes(int G, int Q, int N);
+int retrieve_pair_capacity(int V, int k);
+int launch_vlad(const float* desc, const int32_t* counts, int G, int K, const float* codebook, int C, float* vlad, int32_t* assign, int32_t* n_assigned,
+                int32_t* info, void* ws, hipStream_t st);
+int launch_kmeans_step(const float* desc, const int32_t* counts, int G, int K, const float* codebook, int C, float* codebook_out, int32_t* assign,
+                       int32_t* n_assigned, double* objective, int32_t* info, void* ws, hipStream_t st);
+int launch_retrieve_topk(const float* q, const float* db, const int32_t* n_db, int G, int Q, int N, int D, int k, int exclude_self, int32_t* idx,
+                         float* score, void* ws, hipStream_t st);
+int launch_pairs_from_shortlists(const int32_t* idx, const int32_t* n_views, int S, int V, int k, int32_t* view_pairs, int32_t* n_pairs, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,

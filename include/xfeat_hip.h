@@ -723,6 +723,49 @@ int xfh_verify_matches(const float* kpts, const int32_t* view_pairs, const int64
                        xfh_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image retrieval (DESIGN.md 3.23 / csrc/k_retrieval.hip): which images to match and which map to query.  VLAD global descriptors of
+ * the local descriptors over a codebook learned by spherical k-means from those descriptors, top-k shortlists from the inner
+ * products of the global vectors, and the pair list of a scene from its shortlists.  All fp32 (the k-means objective fp64) in
+ * orders of summation that the shapes fix: two calls give the same bytes.  Asynchronous; no host synchronisation inside.  Every
+ * argument check returns before any launch: XFH_ERR_UNSUPPORTED for C, D, k or V beyond the limits, XFH_ERR_ARG otherwise,
+ * XFH_ERR_WORKSPACE for the workspace (256-byte aligned; the *_workspace_bytes functions return 0 for a bad shape).
+ *   desc (G,K,64) fp32 unit rows (16-byte aligned), counts (G,) int32 or NULL = K (read clamped to [0, K]), codebook (C,64) fp32,
+ *   C in {32, 64, 128, 256}.  Row i of group g is valid iff i < counts[g] and its 64 components are finite.  assign (G,K) int32 =
+ *   the centroid with the largest inner product (a chain over the 64 components) among the finite ones, the lowest index among
+ *   equals; -1 for a row that is not valid or has no finite score.
+ *   xfh_vlad: G K <= 2^24.  Per (group, centroid) the residuals row - codebook[c] of the rows assigned to c are summed in ascending
+ *     row order (chunks of 1024 rows, the chunk sums added ascending); a 64-block whose squared norm n2 is finite and >= FLT_MIN is
+ *     multiplied by 1 / sqrt(n2), any other becomes zero; the vector is multiplied by 1 / sqrt(m), m the number of non-zero blocks.
+ *     vlad (G,C*64) fp32, n_assigned (G,C) int32, info (G,4) int32: valid rows, rows below the count that are not finite, m,
+ *     1 when m = 0 (an all-zero vector).
+ *   xfh_kmeans_step: one step of spherical k-means over the G K <= 2^22 rows as ONE set (in the order (g, i)).  codebook_out (C,64)
+ *     = the ordered sum of the rows of a cluster times 1 / sqrt(n2); a cluster that is empty or whose n2 is not finite or below
+ *     FLT_MIN keeps its centroid.  n_assigned (C,) int32; objective: one fp64 value, the fixed-order sum of the winning scores;
+ *     info (4,) int32: valid rows, rows below the count that are not finite, clusters that kept their centroid, 0.
+ *     codebook_out must not be codebook.
+ *   xfh_retrieve_topk: q (G,Q,D), db (G,N,D) fp32 (16-byte aligned), n_db (G,) int32 or NULL = N; D a multiple of 64, D <= 16384;
+ *     1 <= k <= 128; exclude_self != 0: query j never returns database row j.  The score is the fp32 inner product (chains over
+ *     the 64 components of a block, over the 16 blocks of a segment and over the segments).  idx (G,Q,k) int32, score (G,Q,k) fp32:
+ *     the rows below n_db with a finite score by score descending, then index ascending; -1 and NaN past the number found.
+ *   xfh_pairs_from_shortlists: idx (S,V,k) int32, n_views (S,) int32 or NULL = V, 2 <= V <= 32, k <= 128.  view_pairs (S,Pcap,2)
+ *     int32, Pcap = min(V k, V (V - 1) / 2): the undirected union of the edges (v, idx[s,v,j]) as pairs a < b in ascending (a, b)
+ *     order without duplicates, then (-1, -1); entries that are negative, not below n_views or equal to v are ignored.
+ *     n_pairs (S,) int32.  No workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t xfh_vlad_workspace_bytes(int G, int K, int C);
+int xfh_vlad(const float* desc, const int32_t* counts, int G, int K, const float* codebook, int C, float* vlad, int32_t* assign,
+             int32_t* n_assigned, int32_t* info, void* workspace, size_t workspace_bytes, xfh_stream stream);
+size_t xfh_kmeans_workspace_bytes(int G, int K, int C);
+int xfh_kmeans_step(const float* desc, const int32_t* counts, int G, int K, const float* codebook, int C, float* codebook_out,
+                    int32_t* assign, int32_t* n_assigned, double* objective, int32_t* info, void* workspace,
+                    size_t workspace_bytes, xfh_stream stream);
+size_t xfh_retrieve_workspace_bytes(int G, int Q, int N);
+int xfh_retrieve_topk(const float* q, const float* db, const int32_t* n_db, int G, int Q, int N, int D, int k, int exclude_self,
+                      int32_t* idx, float* score, void* workspace, size_t workspace_bytes, xfh_stream stream);
+int xfh_pairs_from_shortlists(const int32_t* idx, const int32_t* n_views, int S, int V, int k, int32_t* view_pairs,
+                              int32_t* n_pairs, xfh_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fundamental matrix from the matches -- match verification for uncalibrated, non-planar pairs:
  *     F, inliers = cv2.findFundamentalMat(points1, points2, cv2.USAC_MAGSAC, ransac_thr, confidence, maxIters)
  * for P pairs at once.  OpenCV is not part of the reference tree (which never calls it): the algorithm is the published one
