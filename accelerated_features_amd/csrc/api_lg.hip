@@ -237,6 +237,13 @@ __global__ void lg_init_kernel(int32_t* ind0, int n0, int32_t* count0, int32_t* 
         *count1 = live1 ? max(0, min(n1, *live1)) : n1;
     }
 }
+// the rows of both outputs from the count to their capacity: (-1, -1) and 0 (include/xfeat_hip.h), so that no row is left as the caller's buffer held it
+__global__ void lg_pad_kernel(const int32_t* n_out, int out_cap, int64_t* matches, float* scores) {
+    const int o = max(*n_out, 0) + blockIdx.x * 256 + threadIdx.x;
+    if (o >= out_cap) return;
+    matches[2 * (size_t)o] = matches[2 * (size_t)o + 1] = -1;
+    scores[o] = 0.f;
+}
 }  // namespace
 
 size_t xfh_lg_workspace_bytes(int N0, int N1) {
@@ -344,6 +351,7 @@ static int lg_match_impl(xfh_lg_handle h, const float* kpts0, const float* desc0
     }
     launch_lg_assign(w.sim, w.n1pad, nn[0], N0, nn[1], N1, w.s[0].z, w.s[1].z, w.rlse, w.clse, w.m0, w.m1, w.best0, ind[0], ind[1], min_conf,
                      matches, scores, n_matches, w.ascratch, st);
+    lg_pad_kernel<<<ceil_div(std::min(N0, N1), 256), 256, 0, st>>>(n_matches, std::min(N0, N1), matches, scores);
     if (bad) return fail(XFH_ERR_UNSUPPORTED, "xfh_lg_match: missing linear kernel instantiation");
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(XFH_ERR_HIP, "xfh_lg_match: %s", hipGetErrorString(e));

@@ -176,7 +176,10 @@ __global__ __launch_bounds__(1024) void mnn_finalize_kernel(const int32_t* __res
     const int n1 = pair_count(n1p, p * n_stride, N1);
     const int n2 = pair_count(n2p, p * n_stride + n_off2, N2);
     if (n1 <= 0 || n2 <= 0) {
-        if (q == 0 && tid == 0) n_matches[p] = 0;
+        if (q == 0) {
+            if (tid == 0) n_matches[p] = 0;
+            for (int o = tid; o < N1; o += 1024) idx0[(size_t)p * N1 + o] = idx1[(size_t)p * N1 + o] = -1;       // no match: the whole row is padding
+        }
         return;
     }
     if (q * 1024 >= n1) return;
@@ -212,7 +215,12 @@ __global__ __launch_bounds__(1024) void mnn_finalize_kernel(const int32_t* __res
         idx0[(size_t)p * N1 + o] = row;
         idx1[(size_t)p * N1 + o] = m;
     }
-    if (tid == 0 && (q + 1) * 1024 >= n1) n_matches[p] = s_before + tot;       // the pair's last chunk knows the total
+    if ((q + 1) * 1024 >= n1) {                                                // the pair's last chunk knows the total ...
+        if (tid == 0) n_matches[p] = s_before + tot;
+        // ... and writes the padding behind it (-1: include/xfeat_hip.h), so that no entry of idx0 / idx1 is left as the caller's buffer held it.  The
+        // other chunks write ranks below the total only.
+        for (int o = s_before + tot + tid; o < N1; o += 1024) idx0[(size_t)p * N1 + o] = idx1[(size_t)p * N1 + o] = -1;
+    }
 }
 
 int match_debug_occupancy() {

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void refine_rows_kernel(const float* __restric
     }
 }
 
-// grid (P), block 1024: ordered compaction of the kept rows of each pair
+// grid (P), block 1024: ordered compaction of the kept rows of each pair; the rows from the count to N are written as zeros
 __global__ __launch_bounds__(1024) void refine_compact_kernel(const float* __restrict__ rows_tmp,
                                                               const unsigned char* __restrict__ keep_tmp,
                                                               const int32_t* __restrict__ offs, int N,
@@ -120,6 +120,7 @@ __global__ __launch_bounds__(1024) void refine_compact_kernel(const float* __res
         __syncthreads();
     }
     if (tid == 0) n_out[p] = s_base;
+    for (int r = s_base + tid; r < N; r += 1024) *reinterpret_cast<float4*>(out + ((size_t)p * N + r) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 void launch_refine_finish(const float* o, const int32_t* rowmap, const int32_t* offs, const int32_t* total,

@@ -13,6 +13,9 @@
  *     starts with host_.  Layouts are dense, row-major in the index order written.
  *   - The library never allocates in the hot path: the caller provides a workspace of
  *     xfh_*_workspace_bytes() bytes (256-byte aligned).  Only xfh_create allocates (weights).
+ *   - Workspace and outputs need no initialisation -- every word a call reads from them it has written first, and every byte of an
+ *     output is determined by the call's inputs unless its entry says otherwise -- and nothing outside them is written
+ *     (tests/test_gpu_buffers.py holds every entry to this between guard bands, at exactly the named workspace size).
  *   - Every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = the
  *     default stream).  No hidden synchronisation.  Process-wide state is limited to: the
  *     thread-local error string and per-device "kernel attribute set" flags (idempotent).  The library reads
@@ -230,7 +233,7 @@ int xfh_extract_dense(xfh_handle h, const float* reliab, const float* feats, int
  *   itself, ties included, comes from fp32 dot products of d1 / d2 in a fixed summation order.
  *   min_cossim <= 0 disables the similarity test (reference: `if min_cossim > 0`).
  *   pair_stride1/2 are in floats.
- * outputs: idx0, idx1 (P,N1) int64 (idx0 ascending), n_matches (P) int32.
+ * outputs: idx0, idx1 (P,N1) int64 (idx0 ascending), n_matches (P) int32; the entries from n_matches[p] to N1 are written as -1.
  * Arg-max ties resolve to the lowest index, like torch.max / torch.argmax.
  * ---------------------------------------------------------------------------------------- */
 size_t xfh_match_workspace_bytes(int P, int N1, int N2);
@@ -269,7 +272,8 @@ int xfh_match_mnn(xfh_handle h /* may be NULL */, const float* d1, size_t pair_s
  *   A row or column without a passing element has no match.  An all-zero model (what the estimators write where nothing was
  *   found) and a model with a non-finite entry give no matches for their pair.  max_error <= 0 or non-finite: XFH_ERR_ARG.
  *   N2 <= 2^21 (XFH_ERR_UNSUPPORTED beyond).
- * outputs: idx0, idx1 (P,N1) int64 (idx0 ascending), n_matches (P) int32; ties resolve to the lowest index.
+ * outputs: idx0, idx1 (P,N1) int64 (idx0 ascending), n_matches (P) int32, the entries from n_matches[p] to N1 written as -1; ties resolve
+ * to the lowest index.
  * ---------------------------------------------------------------------------------------- */
 #define XFH_GUIDE_FUNDAMENTAL 0
 #define XFH_GUIDE_HOMOGRAPHY  1
@@ -287,8 +291,8 @@ int xfh_match_mnn_guided(const float* d1, size_t pair_stride1, const float* d2, 
  *
  *   desc0/desc1 (P,N,64), kp0/kp1 (P,N,2), scale0 (P,N)  -- detectAndComputeDense outputs
  *   idx0/idx1 (P,N) int64 with n_matches (P) int32 (device) -- xfh_match_mnn outputs
- *   out (P,N,4) fp32 rows (x0,y0,x1,y1) of the matches with conf > fine_conf, order kept;
- *   n_out (P) int32.
+ *   out (P,N,4) fp32 rows (x0,y0,x1,y1) of the matches with conf > fine_conf, order kept, the rows from n_out[p] to N written as
+ *   zeros; n_out (P) int32.
  * ---------------------------------------------------------------------------------------- */
 size_t xfh_refine_workspace_bytes(int P, int N);
 int xfh_refine_matches(xfh_handle h, const float* desc0, const float* desc1, const float* kp0, const float* kp1,
@@ -809,7 +813,8 @@ int xfh_find_fundamental_matches(const float* kpts0, const float* kpts1, int kpt
  *                 layer but the last, a set that still has MORE than this many key-points drops those whose
  *                 matchability is <= 1 - width_confidence (the published pruning_keypoint_thresholds: -1 on CPU =
  *                 always, 1024 on CUDA, 1536 on CUDA with flash attention); XFH_LG_NO_PRUNING disables it.  Output: matches (<= min(N0,N1), 2) int64 indices into the input
- *                 lists, ascending in column 0; scores; n_matches (1) int32 -- all device memory, asynchronous.
+ *                 lists, ascending in column 0; scores; n_matches (1) int32 -- all device memory, asynchronous.  The rows from n_matches
+ *                 to min(N0,N1) are written as (-1,-1) with score 0.
  * ---------------------------------------------------------------------------------------- */
 #define XFH_LG_NO_PRUNING (1 << 30)
 typedef struct xfh_lg_context* xfh_lg_handle;
@@ -832,7 +837,8 @@ int xfh_lg_profile_read(xfh_lg_handle h, int* n_launches, double* total_ms, doub
 /* The batch form used with xfh_detect_sparse's fixed-capacity outputs: frames (2p, 2p+1) of kpts (2P,cap,2) /
  * desc (2P,cap,64) / counts (2P) int32 (all device memory) form pair p; every image has size (W,H).  No host
  * read-back of the counts; pairs run back to back on `stream` and share one workspace of
- * xfh_lg_workspace_bytes(cap, cap).  Outputs: matches (P,cap,2) int64, scores (P,cap), n_matches (P) int32. */
+ * xfh_lg_workspace_bytes(cap, cap).  Outputs: matches (P,cap,2) int64, scores (P,cap), n_matches (P) int32; the rows of pair p from
+ * n_matches[p] to cap are written as (-1,-1) with score 0. */
 int xfh_lg_match_pairs(xfh_lg_handle h, const float* kpts, const float* desc, const int32_t* counts, int P, int cap,
                        float W, float H, float min_conf, int prune_min_kpts, int64_t* matches, float* scores,
                        int32_t* n_matches, void* workspace, size_t workspace_bytes, xfh_stream stream);
