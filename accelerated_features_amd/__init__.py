@@ -15,3 +15,4 @@ from .multiview import baseline_ratios_batch  # noqa: F401
 from .localization import build_map_batch, localize_map_batch, project_map, resect_views_batch  # noqa: F401
 from .retrieval import global_descriptors_batch, retrieve_topk, select_pairs, train_codebook  # noqa: F401
 from .verification import filter_matches_batch, verify_matches_graph  # noqa: F401
+from .cameras import camera_matrix, distort_keypoints, pack_cameras, undistort_images, undistort_keypoints  # noqa: F401

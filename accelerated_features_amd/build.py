@@ -44,7 +44,7 @@ def _sources():
 
 def _deps():
     hdr = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "xfeat_hip.h"))
+    hdr += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("xfeat_hip.h", "xfeat_hip_cameras.h")]
     return hdr
 
 

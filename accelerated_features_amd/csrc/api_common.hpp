@@ -1,6 +1,6 @@
-// What the units of the C ABI (api.hip, api_lg.hip, api_geometry.hip, api_retrieval.hip) share: the error setter and the launch and workspace checks -- each
+// What the units of the C ABI (api.hip, api_lg.hip, api_geometry.hip, api_retrieval.hip, api_cameras.hip) share: the error setter and the launch and workspace checks -- each
 // defined once, in api.hip -- and the limits that the argument checks and the *_workspace_bytes guards name.  Internal: in namespace xfh, so
-// the exported xfh_* symbols are those of include/xfeat_hip.h alone.
+// the exported xfh_* symbols are those of include/xfeat_hip.h and include/xfeat_hip_cameras.h alone.
 #pragma once
 #include "../../include/xfeat_hip.h"      // (size_t)
 

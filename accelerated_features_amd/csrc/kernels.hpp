@@ -191,6 +191,11 @@ int launch_kmeans_step(const float* desc, const int32_t* counts, int G, int K, c
 int launch_retrieve_topk(const float* q, const float* db, const int32_t* n_db, int G, int Q, int N, int D, int k, int exclude_self, int32_t* idx,
                          float* score, void* ws, hipStream_t st);
 int launch_pairs_from_shortlists(const int32_t* idx, const int32_t* n_views, int S, int V, int k, int32_t* view_pairs, int32_t* n_pairs, hipStream_t st);
+// ---- k_cameras.hip (camera models: key-points through a lens model in both directions, rectification of images) ----
+int launch_camera_points(const float* pts, const int32_t* counts, long long P, int K, const int32_t* kind, const double* params, int n_cameras,
+                         const double* k_other, int direction, float* out, unsigned char* status, hipStream_t st);
+int launch_undistort_images(const void* src, int is_f32, int B, int C, int H, int W, const int32_t* kind, const double* params, int n_cameras,
+                            const double* k_new, int Ho, int Wo, double fill, void* dst, unsigned char* valid, hipStream_t st);
 // ---- k_fundamental.hip (7-point MAGSAC++ fundamental matrix + re-weighted 8-point refinement from match lists; FM_7POINT / FM_8POINT) ----
 size_t fundamental_workspace_bytes(int P, int max_iters);
 int launch_find_fundamental(const float* p0, const float* p1, const int64_t* idx0, const int64_t* idx1, int kcap, const int32_t* counts, int n_const,
